@@ -10,7 +10,13 @@ half's SpMM (strong scaling: the graph is fixed, value = all nnz x layers / max-
 time). "roofline" prices the SpMM kernel's algorithmic bytes against HBM peak with its own
 HIP-event time on the stream it runs on.
 
-Phases after the timed steps (each reported in its own key of the same JSON line):
+A plain run sets up the graph, warms up, times the steps and prints the JSON line (value,
+ms_per_step, the SpMM roofline from the events of the timed steps); --dump-outputs DIR also
+writes what the last timed step computed (the final embeddings; a seeded sample of the rows,
+the same from run to run) as DIR/<name>.npy.
+
+Phases after the timed steps, only with --full (each reported in its own key of the same JSON
+line, null in a plain run; at N > 1 also the `comm` block's all-gathers timed alone):
   topk    masked full-catalog top-20 (e0 scores, -1024 exclusion of each user's train+val
           items) for a block of users per rank over all 1M items (recs/s over ranks);
   spread  SpreadLightGCN / LGCNHS for ALL users over all items: item-tiled factored HybridS
@@ -22,7 +28,7 @@ Phases after the timed steps (each reported in its own key of the same JSON line
   cpu_baseline*  the reference's op sequences (oracle restatement) on host cores, bounded
           samples (skip with --no-cpu-baseline).
 
-Run: python bench.py [--gpus N --steps K --warmup W]. N > 1: one process per GPU, either
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. N > 1: one process per GPU, either
 under the caller's torch.distributed.run (WORLD_SIZE must equal N) or started here as a child
 torch.distributed.run when WORLD_SIZE is unset.
 """
@@ -232,11 +238,49 @@ def _sync(dev):
         torch.cuda.synchronize()
 
 
-def time_propagation(shard, dis_l, e0_orig, D, L, steps, warmup, world, dev, layer_fn=None):
+def gathered_output(prop, shard, world):
+    """The forward's last output as a caller of the propagation receives it: [n_nodes, d] in
+    the original node order. At N > 1 every rank's rows are all-gathered first (what
+    forward(gather_out=True) does after its layers); collective, every rank calls it."""
+    from lgcnhs.dist import SegmentShard, _gather_block, _gather_piece
+    if world > 1:
+        if isinstance(shard, SegmentShard):
+            for s_, ps in enumerate(shard.seg_pieces):
+                for c in range(len(ps)):
+                    _gather_piece(prop.out, shard, s_, c, prop.group, async_op=False)
+        else:
+            for c in range(shard.chunks):
+                _gather_block(prop.out, shard, c, prop.group, async_op=False)
+    return shard.unpermute_rows(prop.out)
+
+
+def dump_outputs(path, outputs, budget=48 << 20, seed=0):
+    """--dump-outputs: every array of `outputs` as path/<name>.npy (float32 or float64). An
+    array above `budget` bytes is cut to a fixed, seeded sample of its rows (sorted row ids in
+    <name>_rows.npy, float64), so the files stay under 64 MB in all and two builds run with
+    the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        n = t.shape[0]
+        keep = max(1, budget // max(1, t[0].numel() * t.element_size()))
+        if n > keep:
+            rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"),
+                a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+
+def time_propagation(shard, dis_l, e0_orig, D, L, steps, warmup, world, dev, layer_fn=None,
+                     exchange=True, outputs=None):
     """Time `steps` full L-layer forwards; returns (max-over-ranks seconds, average SpMM
     'launch' seconds = one layer's kernels on this rank, from HIP events on the stream, and
-    at N > 1 the `comm` block). layer_fn: lgcnhs.dist's HIP layer unless given (the CPU
-    launch check passes a host stand-in)."""
+    at N > 1 the `comm` block, which takes a run of the all-gathers alone: only with
+    `exchange`). layer_fn: lgcnhs.dist's HIP layer unless given (the CPU launch check passes a
+    host stand-in). outputs: a dict that receives the last timed step's result as
+    "final_embeddings" (gathered_output)."""
     from lgcnhs.dist import BipartitePropagation, SegmentShard, ShardedPropagation, exposed_wait_ms
     e0 = shard.permute_rows(e0_orig)  # chunk-major layout (identity at N=1)
     cls = BipartitePropagation if isinstance(shard, SegmentShard) else ShardedPropagation
@@ -266,8 +310,11 @@ def time_propagation(shard, dis_l, e0_orig, D, L, steps, warmup, world, dev, lay
         elapsed = float(t.item())
         wait = exposed_wait_ms(prop.waits, L, steps)
         prop.waits = None
-        comm = time_exchange(prop, shard, D, world, dev)
-        comm.update(exposure(wait, comm["allgather_ms_per_layer"], L, world, dev))
+        if exchange:
+            comm = time_exchange(prop, shard, D, world, dev)
+            comm.update(exposure(wait, comm["allgather_ms_per_layer"], L, world, dev))
+    if outputs is not None:
+        outputs["final_embeddings"] = gathered_output(prop, shard, world)
     del prop, e0
     return elapsed, kernel_ms / (steps * L) / 1e3, comm
 
@@ -887,17 +934,10 @@ def _host_layer(shard, piece, dis, x, y, x0, acc, out, mode, denom):
         out[g] = (x0[g] + v) / denom
 
 
-def launch_check(world: int, rank: int, args) -> None:
-    """--launch-check: the rank plumbing alone (process group, one all-reduce, rank 0's
-    JSON line), no GPU work; what the CPU tests drive through launch_ranks(). Rank 0 also
-    runs the propagation CPU baseline on a small CPU graph through the same function and
-    rank rule as the real line, and at N > 1 every rank times the overlapped bipartite
-    forward over gloo through time_propagation, so the N > 1 cpu_baseline and comm fields are
-    exercised without a GPU."""
-    t = torch.ones(1)
-    if world > 1:
-        dist.all_reduce(t)
-    g = torch.Generator().manual_seed(0)  # a small symmetric bipartite CSR, built on CPU
+def launch_check_inputs():
+    """The launch check's inputs, built on the CPU from one seed: a small symmetric bipartite
+    CSR (U users, I items; rowptr int64, src int32), its deg^-1/2 and e0 [U + I, 16]."""
+    g = torch.Generator().manual_seed(0)
     U, I = 300, 400
     keys = torch.unique(torch.randint(0, U, (5000,), generator=g) * I +
                         torch.randint(0, I, (5000,), generator=g))
@@ -907,17 +947,34 @@ def launch_check(world: int, rank: int, args) -> None:
     rows, src = rows[order], cols[order].to(torch.int32)
     rp = torch.zeros(U + I + 1, dtype=torch.int64)
     rp[1:] = torch.cumsum(torch.bincount(rows, minlength=U + I), 0)
+    deg = (rp[1:] - rp[:-1]).float()
+    dis = torch.where(deg > 0, deg.pow(-0.5), torch.zeros_like(deg))
+    e0 = torch.randn(U + I, 16, generator=g) * 0.1
+    return U, I, rp, src, dis, e0
+
+
+def launch_check(world: int, rank: int, args) -> None:
+    """--launch-check: the rank plumbing alone (process group, one all-reduce, rank 0's
+    JSON line), no GPU work; what the CPU tests drive through launch_ranks(). Rank 0 also
+    runs the propagation CPU baseline on a small CPU graph through the same function and
+    rank rule as the real line, and at N > 1 every rank times the overlapped bipartite
+    forward over gloo through time_propagation, so the N > 1 cpu_baseline and comm fields
+    (and with --dump-outputs the all-gathered output) are exercised without a GPU."""
+    t = torch.ones(1)
+    if world > 1:
+        dist.all_reduce(t)
+    U, I, rp, src, dis, e0 = launch_check_inputs()
     comm = None
     if world > 1:
         # the N > 1 line's comm block through the real timing code: the bipartite shards and
         # the overlapped forward over gloo, a host stand-in for the HIP layer
         from lgcnhs.dist import SegmentShard
         shard = SegmentShard(rp, src, [0, U, U + I], rank, world, "cpu", chunks=2)
-        deg = (rp[1:] - rp[:-1]).float()
-        dis = torch.where(deg > 0, deg.pow(-0.5), torch.zeros_like(deg))
-        e0 = torch.randn(U + I, 16, generator=g) * 0.1
+        outputs = {} if args.dump_outputs else None
         _, _, comm = time_propagation(shard, shard.permute_rows(dis), e0, 16, 3, 2, 1, world,
-                                      "cpu", layer_fn=_host_layer)
+                                      "cpu", layer_fn=_host_layer, outputs=outputs)
+        if outputs is not None and rank == 0:  # the N > 1 gather of --dump-outputs
+            dump_outputs(args.dump_outputs, outputs)
     cpu = None
     if wants_cpu_baseline(rank, args):
         cpu = cpu_baseline(rp, src, U + I, 16, 3, target_nnz=4000, reps=1)
@@ -966,6 +1023,14 @@ def main():
                          "power-law input of SURVEY.md §8(d))")
     ap.add_argument("--launch-check", action="store_true",
                     help="rank plumbing only (process group + one all-reduce), no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed propagation also run every other phase (top-K, "
+                         "spread + eval, train, other widths and graphs, the ML-1M shape, the "
+                         "CPU baselines and parity checks, the N > 1 exchange alone); without "
+                         "it their keys of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the final embeddings, a "
+                         "seeded row sample) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rc = launch_ranks(args)
@@ -981,6 +1046,10 @@ def main():
             dist.init_process_group(args.backend if args.backend != "nccl" else "gloo")
         launch_check(world, rank, args)
         return
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_topk = args.no_spread = args.no_train = True
+        args.no_small = True
+        args.extra_dims, args.other_graphs = [], []
     if world > 1:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.cuda.set_device(local)
@@ -1036,8 +1105,14 @@ def main():
     log(f"[rank {rank}] graph U={U} I={I} nnz={nnz} rows {getattr(shard, 'ranges', None) or (shard.g0, shard.g1)} "
         f"setup {time.time() - t0:.1f}s")
 
+    outputs = {} if args.dump_outputs else None
     elapsed, avg_kernel_s, comm = time_propagation(shard, dis_l, e0_orig, D, L, args.steps,
-                                                   args.warmup, world, dev)
+                                                   args.warmup, world, dev, exchange=args.full,
+                                                   outputs=outputs)
+    if outputs is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        outputs = None
     edge_layers = nnz * L * args.steps
     value = edge_layers / elapsed
     # algorithmic bytes per SpMM launch: nnz*(8+4d) + rows*(4+4d)
@@ -1153,6 +1228,7 @@ def main():
             "metric": "propagation edges/sec + full-catalog top-K recs/sec, 1/2/4/8 MI355X",
             "value": value, "unit": "edge-layers/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic (uniform bipartite, seed 0; e0 ~ N(0, 0.1^2))",
             "config": {"workload": args.workload, "users": U, "items": I, "interactions": E,

@@ -7,5 +7,5 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out/${1:-rehearsal}; mkdir -p $O
 timeout -k 10 900 python3 bench.py --gpus 2 --backend gloo --same-device --workload ${2:-c4} \
-  --steps 3 --warmup 1 --topk-users 8192 --extra-dims > $O/line.json 2> $O/err.log
+  --full --steps 3 --warmup 1 --topk-users 8192 --extra-dims > $O/line.json 2> $O/err.log
 rc=$?; echo "rehearsal rc=$rc"; tail -5 $O/err.log; cut -c1-1500 $O/line.json; exit $rc

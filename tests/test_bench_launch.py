@@ -86,6 +86,85 @@ def test_topk_roofline_prices_the_screen_the_seed_pass_and_the_exact_chains():
     assert abs(r2["achieved"] - base * (1 + 1 / 16) / t / 1e12) < 1e-9 * r2["achieved"]
 
 
+def test_dump_outputs_writes_the_last_steps_result_as_a_seeded_sample(tmp_path):
+    """--dump-outputs: time_propagation hands back what its last timed step computed (the
+    [n_nodes, d] final embeddings in the original node order, here over the host stand-in of
+    the HIP layer against the dense mean of A_hat^l e0), and dump_outputs writes it as float32
+    .npy: whole when it fits the byte budget, else a sorted row sample that depends only on
+    the seed and the shape, its row ids beside it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    from lgcnhs.dist import RowShard
+    g = torch.Generator().manual_seed(0)
+    U, I, D, L = 30, 41, 8, 3
+    n = U + I
+    keys = torch.unique(torch.randint(0, U, (300,), generator=g) * I +
+                        torch.randint(0, I, (300,), generator=g))
+    A = torch.zeros(n, n, dtype=torch.float64)
+    A[keys // I, keys % I + U] = 1
+    A = A + A.T
+    rp = torch.zeros(n + 1, dtype=torch.int64)
+    rp[1:] = torch.cumsum((A != 0).sum(1), 0)
+    src = A.nonzero()[:, 1].to(torch.int32)
+    deg = (rp[1:] - rp[:-1]).float()
+    dis = torch.where(deg > 0, deg.pow(-0.5), torch.zeros_like(deg))
+    e0 = torch.randn(n, D, generator=g)
+    shard = RowShard(rp, src, n, 0, 1, "cpu", chunks=2)
+    outs = {}
+    bench.time_propagation(shard, shard.permute_rows(dis), e0, D, L, 2, 1, 1, "cpu",
+                           layer_fn=bench._host_layer, outputs=outs)
+    got = outs["final_embeddings"]
+    Ah = dis.double()[:, None] * A * dis.double()[None, :]
+    want, cur = e0.double().clone(), e0.double()
+    for _ in range(L):
+        cur = Ah @ cur
+        want += cur
+    want /= L + 1
+    assert got.shape == (n, D) and (got.double() - want).abs().max() < 1e-5
+
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    whole = np.load(tmp_path / "a" / "final_embeddings.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, got.numpy())
+    assert not (tmp_path / "a" / "final_embeddings_rows.npy").exists()
+    for d in ("b", "c"):  # a budget of 10 rows: the same sample both times
+        bench.dump_outputs(str(tmp_path / d), outs, budget=10 * D * 4)
+    rows = np.load(tmp_path / "b" / "final_embeddings_rows.npy")
+    part = np.load(tmp_path / "b" / "final_embeddings.npy")
+    assert rows.dtype == np.float64 and rows.shape == (10,) and np.all(np.diff(rows) > 0)
+    assert part.dtype == np.float32 and np.array_equal(part, whole[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "final_embeddings_rows.npy"))
+    assert np.array_equal(part, np.load(tmp_path / "c" / "final_embeddings.npy"))
+
+
+def test_gpus_2_dump_outputs_gathers_every_ranks_rows(tmp_path):
+    """--dump-outputs at N > 1: rank 0 writes all ranks' rows of the last step's output, in
+    the original node order (the launch check's small graph, two gloo ranks, against the
+    dense mean of A_hat^l e0 over the same inputs)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    p = _run(["--gpus", "2", "--backend", "gloo", "--launch-check", "--no-cpu-baseline",
+              "--dump-outputs", str(tmp_path)], _env())
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = np.load(tmp_path / "final_embeddings.npy")
+    U, I, rp, src, dis, e0 = bench.launch_check_inputs()
+    n = U + I
+    rows = torch.repeat_interleave(torch.arange(n), rp[1:] - rp[:-1])
+    A = torch.zeros(n, n, dtype=torch.float64)
+    A[rows, src.long()] = 1
+    Ah = dis.double()[:, None] * A * dis.double()[None, :]
+    want, cur = e0.double().clone(), e0.double()
+    for _ in range(3):
+        cur = Ah @ cur
+        want += cur
+    want /= 4
+    assert got.dtype == np.float32 and got.shape == (n, 16)
+    assert np.abs(got - want.numpy()).max() < 1e-6
+
+
 def test_gpus_2_line_carries_the_exchange_exposure():
     """The N > 1 line's comm block (what the first SCALE run is read by): the all-gathers
     timed alone (allgather_ms_per_layer, algbw / busbw as nccl-tests define them), and the
