@@ -40,7 +40,7 @@ enum lg_status {
 };
 
 /* ABI version of this header (bumped on any signature change). */
-#define LG_ABI_VERSION 15
+#define LG_ABI_VERSION 16
 int lg_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char *lg_last_error(void);
@@ -150,6 +150,39 @@ int lg_spmm_long_rows_masked_f32(const int64_t *seg_beg, const int64_t *seg_end,
                                  lg_stream_t stream);
 int lg_mark_neighbors_u8(const int64_t *rowptr, const int32_t *src, int64_t n_rows,
                          const uint8_t *in_mask, uint8_t *out_mask, lg_stream_t stream);
+
+/* fp16 layer storage (opt-in, inference): the same propagation call sites
+ * (model/LightGCN/model.py:61-69, model/LightGCNOpti/model.py:74) with the per-layer
+ * embeddings e^l held as IEEE binary16 between layers, so a layer gathers 2*dim bytes per
+ * edge instead of 4*dim. Only the gather operand is 16-bit:
+ *   xh^0 = f16(e0)                       lg_rows_f32_to_f16: round to nearest even,
+ *                                        subnormals kept, |v| > 65504 -> +-inf, NaN -> NaN
+ *   v[g] = sum_e w_e * f32(xh[s_e])      the products, additions and order of
+ *                                        lg_spmm_layer_f32 run on the widened input f32(xh):
+ *                                        v is that call's result bit for bit (ordinary rows
+ *                                        and, through lg_spmm_long_rows_f16, hub rows)
+ *   yh[g] = f16(v[g])                    if yh != NULL: the next layer's operand
+ *   acc_mode epilogue                    as lg_spmm_layer_f32, in fp32 on the unrounded v;
+ *                                        x0 (the fp32 e0), acc and out stay fp32
+ * xh, yh are [*, dim] binary16 arrays indexed by node id (8-byte aligned rows: dim in
+ * {32, 64, 128, 256}); yh must not alias xh. Every other argument, the argument checks and
+ * the long_threshold contract are lg_spmm_layer_f32's / lg_spmm_long_rows_f32's (the
+ * `partial` workspace stays fp32 [n_seg, dim]; segments are added in order). No allocation,
+ * no host sync. lg_rows_f32_to_f16 converts n_rows * dim contiguous values (xh must not
+ * alias x). */
+int lg_rows_f32_to_f16(const float *x, int64_t n_rows, int32_t dim, void *xh,
+                       lg_stream_t stream);
+int lg_spmm_layer_f16(const int64_t *rowptr, const int32_t *src, const float *dis,
+                      const float *w, const void *xh, void *yh, const float *x0, float *acc,
+                      float *out, int64_t n_rows, int64_t row_offset, int32_t dim,
+                      int32_t acc_mode, float denom, int64_t long_threshold,
+                      lg_stream_t stream);
+int lg_spmm_long_rows_f16(const int64_t *seg_beg, const int64_t *seg_end,
+                          const int32_t *seg_node, int64_t n_seg, const int32_t *long_node,
+                          const int64_t *seg_ptr, int64_t n_long, const int32_t *src,
+                          const float *dis, const float *w, const void *xh, void *yh,
+                          const float *x0, float *acc, float *out, int32_t dim,
+                          int32_t acc_mode, float denom, float *partial, lg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Full-catalog scoring with exclusion mask and top-K.

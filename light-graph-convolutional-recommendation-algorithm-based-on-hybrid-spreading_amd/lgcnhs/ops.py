@@ -37,11 +37,23 @@ def run_layer(rowptr, src, dis, w, x, y, x0, acc, out, n_rows: int, row_offset: 
     lg_spmm_layer_live_f32 when a uint8 per-node ``live`` mask marks x's non-zero rows, or
     lg_spmm_layer_rows_f32 computing only the rows a uint8 per-node ``row_mask`` marks)
     and, when the slice has rows above the long-row threshold, lg_spmm_long_rows_f32 (its
-    masked form with row_mask)."""
+    masked form with row_mask). A float16 ``x`` (fp16 layer storage, inference) goes to
+    lg_spmm_layer_f16 / lg_spmm_long_rows_f16: ``y`` is then float16 or None, and live /
+    row_mask (training paths) are refused."""
     dim = x.shape[1]
     thr = plan.threshold if (plan is not None and plan.n_long) else 0
     strm = N.stream_handle(x.device)
-    if row_mask is not None:
+    half = x.dtype == torch.float16
+    if half:
+        if live is not None or row_mask is not None:
+            raise ValueError("float16 layer storage is inference-only: no live / row_mask")
+        if y is not None and y.dtype != torch.float16:
+            raise ValueError(f"a float16 x needs a float16 y (or None), got {y.dtype}")
+        N.check(N.lib().lg_spmm_layer_f16(
+            N.ptr(rowptr), N.ptr(src), N.ptr(dis), N.ptr(w), N.ptr(x), N.ptr(y), N.ptr(x0),
+            N.ptr(acc), N.ptr(out), n_rows, row_offset, dim, mode, float(denom), thr, strm),
+            "lg_spmm_layer_f16")
+    elif row_mask is not None:
         if live is not None:
             raise ValueError("row_mask and live are exclusive")
         N.check(N.lib().lg_spmm_layer_rows_f32(
@@ -66,7 +78,9 @@ def run_layer(rowptr, src, dis, w, x, y, x0, acc, out, n_rows: int, row_offset: 
                 N.ptr(plan.long_node), N.ptr(plan.seg_ptr), plan.n_long, N.ptr(src),
                 N.ptr(dis), N.ptr(w), N.ptr(x), N.ptr(y), N.ptr(x0), N.ptr(acc), N.ptr(out),
                 dim, mode, float(denom), N.ptr(part))
-        if row_mask is not None:
+        if half:
+            N.check(N.lib().lg_spmm_long_rows_f16(*args, strm), "lg_spmm_long_rows_f16")
+        elif row_mask is not None:
             N.check(N.lib().lg_spmm_long_rows_masked_f32(*args, N.ptr(row_mask), strm),
                     "lg_spmm_long_rows_masked_f32")
         else:
@@ -92,17 +106,65 @@ def live_rows(x: torch.Tensor) -> torch.Tensor:
     return (x != 0).any(dim=1).to(torch.uint8)
 
 
+def rows_to_f16(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """f16(x) of an fp32 [n, d] array, round to nearest even (lg_rows_f32_to_f16)."""
+    x = _f32(x, "x")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    N.check(N.lib().lg_rows_f32_to_f16(N.ptr(x), x.shape[0], x.shape[1], N.ptr(out),
+                                       N.stream_handle(x.device)), "lg_rows_f32_to_f16")
+    return out
+
+
+def _check_store(store, sparse_input: bool = False) -> None:
+    if store is None:
+        return
+    if store != torch.float16:
+        raise ValueError(f"layer storage {store} is not supported (torch.float16 or None)")
+    if sparse_input:
+        raise ValueError("store and sparse_input are exclusive (fp16 storage is inference-only)")
+
+
+def _acc_mode(l: int, layers: int) -> int:
+    first, last = l == 0, l == layers - 1
+    if first and last:
+        return N.LG_ACC_ONLY
+    if first:
+        return N.LG_ACC_FIRST
+    return N.LG_ACC_LAST if last else N.LG_ACC_MID
+
+
+def _propagate_mean_f16(adj: Adjacency, e0: torch.Tensor, layers: int) -> torch.Tensor:
+    """propagate_mean with the layer embeddings held as float16 between layers: xh^0 =
+    f16(e0), each layer gathers float16 rows, sums in fp32 exactly as lg_spmm_layer_f32 does
+    on the widened rows, and writes the next float16 operand; the layer mean takes the fp32
+    e0 and the unrounded fp32 layer sums. Two float16 ping-pong buffers."""
+    out = torch.empty_like(e0)
+    bufs = [torch.empty(e0.shape, dtype=torch.float16, device=e0.device),
+            torch.empty(e0.shape, dtype=torch.float16, device=e0.device) if layers > 1 else None]
+    x = rows_to_f16(e0, bufs[0])
+    for l in range(layers):
+        y = None if l == layers - 1 else bufs[(l + 1) % 2]
+        spmm_layer(adj, x, y, e0, out, out, _acc_mode(l, layers), layers + 1)
+        x = y
+    return out
+
+
 def propagate_mean(adj: Adjacency, e0: torch.Tensor, layers: int,
-                   sparse_input: bool = False) -> torch.Tensor:
+                   sparse_input: bool = False, store=None) -> torch.Tensor:
     """mean_{l=0..L} A_hat^l e0 with A_hat = D^-1/2 A D^-1/2 (no autograd). With
     sparse_input (the backward pass: e0 = dL/d(e_final), non-zero on a mini-batch's rows),
     each layer whose input has < LIVE_FRACTION non-zero rows gathers only those rows
-    (lg_spmm_layer_live_f32; same sums)."""
+    (lg_spmm_layer_live_f32; same sums). ``store=torch.float16`` (inference): the gathered
+    layer embeddings are held in 16 bits (lg_spmm_layer_f16; e0 fp32 in, fp32 out)."""
+    _check_store(store, sparse_input)
     e0 = _f32(e0, "e0")
     if e0.shape[0] != adj.n_nodes:
         raise ValueError(f"e0 has {e0.shape[0]} rows, graph has {adj.n_nodes} nodes")
     if layers <= 0:
         return e0.clone()
+    if store is not None:
+        return _propagate_mean_f16(adj, e0, layers)
     out = torch.empty_like(e0)
     bufs = [torch.empty_like(e0), torch.empty_like(e0) if layers > 2 else None]
     x = e0
@@ -268,7 +330,16 @@ class _Propagate(torch.autograd.Function):
         return gin, None, None
 
 
-def propagate(adj: Adjacency, e0: torch.Tensor, layers: int) -> torch.Tensor:
+def propagate(adj: Adjacency, e0: torch.Tensor, layers: int, store=None) -> torch.Tensor:
+    """The L-layer forward with autograd. ``store=torch.float16`` holds the layer embeddings
+    in 16 bits and is inference-only (the backward pass stays fp32): it raises when a
+    gradient would be recorded."""
+    if store is not None:
+        _check_store(store)
+        if e0.requires_grad and torch.is_grad_enabled():
+            raise ValueError("store=torch.float16 is inference-only: run under "
+                             "torch.no_grad() (training propagates in fp32)")
+        return propagate_mean(adj, e0, layers, store=store)
     if e0.requires_grad and torch.is_grad_enabled():
         return _Propagate.apply(e0, adj, layers)
     return propagate_mean(adj, e0, layers)

@@ -8,6 +8,11 @@ from lgcnhs.graph import as_adjacency
 
 
 class LightGCNOpti(nn.Module):
+    # torch.float16: forward() under torch.no_grad() holds the per-layer embeddings in 16
+    # bits between layers (ops.propagate(store=...): half the gathered bytes, final embeddings
+    # within the 1e-4 contract); with grad enabled, and in forward_rows, propagation is fp32.
+    layer_storage = None
+
     def __init__(self, user_num: int, item_num: int, embedding_dim: int, layers: int,
                  user_features: torch.Tensor, item_features: torch.Tensor) -> None:
         super().__init__()
@@ -27,9 +32,15 @@ class LightGCNOpti(nn.Module):
     def forward(self, edge_index) -> tuple:
         w_u, w_i = self.users_emb.weight, self.items_emb.weight
         adj = as_adjacency(edge_index, self.user_num + self.item_num, device=w_u.device)
-        emb_final = ops.propagate(adj, torch.cat([w_u, w_i]), self.layers)
+        emb_final = ops.propagate(adj, torch.cat([w_u, w_i]), self.layers,
+                                  store=self._store())
         users_final, items_final = torch.split(emb_final, [self.user_num, self.item_num])
         return users_final, w_u, items_final, w_i
+
+    def _store(self):
+        """The layer storage forward() propagates with: layer_storage when no gradient is
+        being recorded, else None (fp32)."""
+        return None if torch.is_grad_enabled() else self.layer_storage
 
     def forward_rows(self, edge_index, nodes: torch.Tensor) -> torch.Tensor:
         """The final embeddings of forward() at node ids ``nodes`` (users 0..U-1, items
