@@ -40,7 +40,7 @@ enum lg_status {
 };
 
 /* ABI version of this header (bumped on any signature change). */
-#define LG_ABI_VERSION 16
+#define LG_ABI_VERSION 17
 int lg_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). */
 const char *lg_last_error(void);
@@ -233,6 +233,27 @@ int lg_score_topk_screened_f32(const float *eu, const float *ei, const void *eu_
                                const int32_t *ex_col, float mask_value, int32_t k,
                                int32_t n_splits, float *out_val, int64_t *out_idx, void *ws,
                                size_t ws_bytes, lg_stream_t stream);
+
+/* lg_score_topk_f32 for every k in [1, 1024] (csrc/topk_wide.hip K2w): the torch.topk(score, k)
+ * of model/LightGCN/recommend.py:83-114 (same code: LightGCNOpti/recommend.py:83-114,
+ * LightGCN/evaluation.py:31-51) at any RECOMMEND["k"] up to 1024. The contract is
+ * lg_score_topk_f32's: the same score chain, mask, order (score desc, item asc), padding
+ * (-inf / -1 when fewer than k items rank; NaN and -inf scores never rank), dim in
+ * {32, 64, 128} and n_splits in [1, 4096]; for k <= 128 the outputs equal
+ * lg_score_topk_f32's bit for bit. Each (split, user) keeps its candidate list in a slab of
+ * 512 / 1024 / 2048 8-byte entries (k <= 256 / 512 / 1024) of the workspace, so the workspace
+ * is always needed: lg_score_topk_wide_ws_bytes = splits x n_users x slab bytes (0 for
+ * arguments the call refuses), 8-byte aligned. A caller short of memory passes user blocks
+ * (eu rows and the matching ex_rowptr slice, as lgcnhs.ops.score_topk does).
+ * LG_ERR_WORKSPACE when ws is NULL or short; LG_ERR_ARG on a null pointer, bad dim, k or
+ * n_splits, a half-set exclusion pair or a misaligned ws, before any launch. n_users = 0
+ * returns LG_OK. Never allocates, never syncs. */
+size_t lg_score_topk_wide_ws_bytes(int64_t n_users, int64_t n_items, int32_t dim, int32_t k,
+                                   int32_t n_splits);
+int lg_score_topk_wide_f32(const float *eu, const float *ei, int64_t n_users, int64_t n_items,
+                           int32_t dim, const int64_t *ex_rowptr, const int32_t *ex_col,
+                           float mask_value, int32_t k, int32_t n_splits, float *out_val,
+                           int64_t *out_idx, void *ws, size_t ws_bytes, lg_stream_t stream);
 
 /* Dense masked score matrix G[u][i] (same score definition and mask as above), written
  * with leading dimension ldg. Replaces getAllocateMat's matmul + masks

@@ -2,6 +2,7 @@
 
 propagate        LightGCN layers + layer mean      model/LightGCN/model.py:53-74
 score_topk       e0 scores, -1024 mask, top-k      model/LightGCN/recommend.py:83-114
+                 (k <= 128: K2 / K2r; 128 < k <= 1024: K2w, lists in global slabs)
 score_dense      masked dense score matrix G       model/SpreadLightGCN/model.py:74-104
 spread_general   general_W                         model/SpreadMethod/model.py:14-27
 hybrid_weight    HybridS W                         model/SpreadMethod/model.py:63-85
@@ -353,8 +354,25 @@ def _resident_blocks(device, k: int = 64, screen: bool = False) -> int:
     return per_cu * torch.cuda.get_device_properties(device).multi_processor_count
 
 
+WIDE_K_MIN, WIDE_K_MAX = 129, 1024  # lg_score_topk_wide_f32's share of score_topk's k
+# score_topk's wide path (128 < k <= 1024) keeps a slab of 512 / 1024 / 2048 8-byte entries
+# per (split, user) in its workspace: 512 MiB per split for 32,768 users at k = 1024. Above
+# this many bytes it runs consecutive user blocks instead.
+WIDE_WS_CAP_BYTES = 1 << 30
+
+
+def _wide_resident_blocks(device, k: int, d: int = 64) -> int:
+    """Workgroups of k_score_topk_wide resident at once: 4 waves and 17 / 33 / 65 KiB of LDS
+    each (k <= 256 / 512 / 1024), 106 VGPRs at d = 64 and 158 at d = 128."""
+    per_cu = 2 if k > 512 else (3 if d > 64 else 4)
+    return per_cu * torch.cuda.get_device_properties(device).multi_processor_count
+
+
 def _users_per_block(k: int, screen: bool = False, d: int = 64) -> int:
-    """Users per workgroup of csrc/topk.hip's launches (dispatch_topk / _screen)."""
+    """Users per workgroup of csrc/topk.hip's launches (dispatch_topk / _screen) and, for
+    k > 128, of csrc/topk_wide.hip's (4 waves x 16 users)."""
+    if k > 128:
+        return 64
     if screen:  # (8 waves x 2 groups; k > 64 at d <= 64: 1 group, LG_GL4_NG)
         return 128 if k > 64 and d <= 64 else 256
     return 128 if k <= 32 else (64 if k <= 64 else 32)
@@ -434,10 +452,22 @@ def score_topk(eu: torch.Tensor, ei: torch.Tensor, k: int, excl: RowSets | None 
     indices int64 [U,k]) sorted by (score desc, item asc). screen=True runs
     lg_score_topk_screened_f32: a bf16 MFMA bound decides which 16-item tiles get the exact
     fp32 chain; the results are lg_score_topk_f32's (screen=False) bit for bit. Default:
-    SCREEN_DEFAULT where it pays for the shape (screen_pays)."""
+    SCREEN_DEFAULT where it pays for the shape (screen_pays).
+
+    128 < k <= 1024 runs lg_score_topk_wide_f32 (same score, mask, order and padding; the
+    lists live in workspace slabs). There is no screened wide kernel: screen=True raises.
+    When the slabs would pass WIDE_WS_CAP_BYTES the users are processed in consecutive
+    blocks; the result does not depend on the blocking."""
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
     nu, d = eu.shape
     ni = ei.shape[0]
+    k = int(k)
+    if k > WIDE_K_MAX:
+        raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
+    if k >= WIDE_K_MIN:
+        if screen:
+            raise ValueError(f"screen=True takes k <= 128 (k={k}): no screened wide kernel")
+        return _score_topk_wide(eu, ei, k, excl, mask_value, n_splits)
     if screen is None:
         screen = SCREEN_DEFAULT and screen_pays(nu, ni, k)
     if ei.shape[1] != d:
@@ -469,6 +499,68 @@ def score_topk(eu: torch.Tensor, ei: torch.Tensor, k: int, excl: RowSets | None 
         N.ptr(eu), N.ptr(ei), nu, ni, d, ex_rp, ex_c, float(mask_value), int(k), ns,
         N.ptr(val), N.ptr(idx), N.ptr(ws), ws_bytes, N.stream_handle(eu.device)),
         "lg_score_topk_f32")
+    return val, idx
+
+
+def _wide_user_block(nu: int, ni: int, d: int, k: int, ns: int, cap_bytes: int) -> int:
+    """Users per lg_score_topk_wide_f32 call so that its workspace stays within cap_bytes: all
+    of them when that fits, else the largest multiple of the kernel's 64 users per workgroup
+    that does (at least one workgroup)."""
+    ws_fn = N.lib().lg_score_topk_wide_ws_bytes
+    if nu <= 0 or ws_fn(nu, ni, d, k, ns) <= cap_bytes:
+        return max(nu, 1)
+    upb = _users_per_block(k, False, d)
+    per_wg = ws_fn(upb, ni, d, k, ns)
+    return upb * max(1, cap_bytes // max(per_wg, 1))
+
+
+def _wide_plan(nu: int, ni: int, d: int, k: int, resident: int, cap_bytes: int):
+    """(users per call, item splits) of the wide path: _splits_for's cost (rounds of resident
+    workgroups per split, 2 % per split) summed over the calls that cap_bytes of slabs force.
+    With every user in one call this is _splits_for's choice; under a tight cap more splits
+    mean fewer users per call, so the fewest splits that fill the slabs win."""
+    per_block = _users_per_block(k, False, d)
+    best, best_cost = (max(nu, 1), 1), None
+    for s in range(1, min(64, max(1, ni // 256)) + 1):
+        blk = min(max(nu, 1), _wide_user_block(nu, ni, d, k, s, cap_bytes))
+        tiles = -(-blk // per_block)
+        calls = -(-max(nu, 1) // blk)
+        cost = calls * -(-tiles * s // resident) / s * (1 + 0.02 * s)
+        if best_cost is None or cost < best_cost - 1e-12:
+            best, best_cost = (blk, s), cost
+    return best
+
+
+def _score_topk_wide(eu, ei, k: int, excl, mask_value: float, n_splits):
+    """score_topk for 128 < k <= 1024 (also callable below: lg_score_topk_wide_f32 takes any
+    k in [1, 1024]), in user blocks of at most WIDE_WS_CAP_BYTES of workspace."""
+    nu, d = eu.shape
+    ni = ei.shape[0]
+    if ei.shape[1] != d:
+        raise ValueError("eu/ei dims differ")
+    if excl is not None and excl.n_rows != nu:
+        raise ValueError(f"exclusion rows {excl.n_rows} != users {nu}")
+    val = torch.empty((nu, k), dtype=torch.float32, device=eu.device)
+    idx = torch.empty((nu, k), dtype=torch.int64, device=eu.device)
+    if nu == 0:
+        return val, idx
+    resident = _wide_resident_blocks(eu.device, k, d)
+    if n_splits is None:
+        blk, ns = _wide_plan(nu, ni, d, k, resident, WIDE_WS_CAP_BYTES)
+    else:
+        ns = int(n_splits)
+        blk = _wide_user_block(nu, ni, d, k, ns, WIDE_WS_CAP_BYTES)
+    ws_bytes = N.lib().lg_score_topk_wide_ws_bytes(min(blk, nu), ni, d, k, ns)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=eu.device)
+    for u0 in range(0, nu, blk):
+        u1 = min(nu, u0 + blk)
+        n = u1 - u0
+        ex = excl.slice_rows(u0, u1) if excl is not None else None
+        N.check(N.lib().lg_score_topk_wide_f32(
+            N.ptr(eu[u0:u1]), N.ptr(ei), n, ni, d, N.ptr(ex.rowptr if ex else None),
+            N.ptr(ex.col if ex else None), float(mask_value), k, ns, N.ptr(val[u0:u1]),
+            N.ptr(idx[u0:u1]), N.ptr(ws), ws_bytes, N.stream_handle(eu.device)),
+            "lg_score_topk_wide_f32")
     return val, idx
 
 

@@ -5,7 +5,8 @@ recommendForAllUser scores with the layer-0 embeddings, masks train and val posi
 -1024 and takes the top-k — in one HIP kernel (lg_score_topk_screened_f32: a bf16 MFMA
 screen, the exact fp32 chain of lg_score_topk_f32 on the tiles it cannot rule out, the same
 lists bit for bit) that never holds the U x I score matrix; ties are ordered (score desc,
-item asc).
+item asc). RECOMMEND["k"] up to 128 takes that kernel; 128 < k <= 1024 takes
+lg_score_topk_wide_f32 (the same scores and order, lists in global slabs); larger k raises.
 """
 import numpy as np
 import pandas as pd
