@@ -307,12 +307,25 @@ int lg_spread_resource_f64(const int64_t *user_rowptr, const int32_t *user_items
  *   excl_mode NONE: nothing is removed (the unfiltered ProbS/movielens branch,
  *                   model/SpreadMethod/recommend.py:49-50).
  * With a G factor the exclusions must be DROP (G's -1024 mask is then never observable).
- * k in [1, 128]. Rows with fewer than k survivors are padded with index -1. */
+ * k in [1, 128] (lg_rows_topk_wide_f64 below takes k up to 1024). Rows with fewer than k
+ * survivors are padded with index -1. */
 enum lg_excl_mode { LG_EXCL_DROP = 0, LG_EXCL_NONE = 1 };
 int lg_rows_topk_f64(const double *F, int64_t ldf, int64_t n_rows, int64_t n_cols,
                      const float *eu, const float *ei, int32_t dim,
                      const int64_t *ex_rowptr, const int32_t *ex_col, int32_t excl_mode,
                      int32_t k, double *out_val, int64_t *out_idx, lg_stream_t stream);
+
+/* lg_rows_topk_f64 for k in [1, 1024]: the reference's argsort + filter + [:k] takes any
+ * RECOMMEND["k"] (model/SpreadMethod/recommend.py:31-50, model/SpreadLightGCN/recommend.py;
+ * G * F: model/SpreadLightGCN/model.py:151). Same arguments, values, admission (v > the
+ * K-th value: NaN and -inf never rank), order (value desc, column asc), exclusion modes and
+ * {-inf, -1} padding; the candidate lists live in LDS (512 / 1024 / 2048 entries for
+ * k <= 256 / 512 / 1024), no workspace. At k <= 128 its lists are lg_rows_topk_f64's bit for
+ * bit. */
+int lg_rows_topk_wide_f64(const double *F, int64_t ldf, int64_t n_rows, int64_t n_cols,
+                          const float *eu, const float *ei, int32_t dim,
+                          const int64_t *ex_rowptr, const int32_t *ex_col, int32_t excl_mode,
+                          int32_t k, double *out_val, int64_t *out_idx, lg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Factored spreading over item tiles: the path for catalogs whose I x I general_W / W do
@@ -408,10 +421,18 @@ int lg_spread_tile_seek(const int64_t *user_rowptr, const int32_t *user_items,
  * (value desc, index asc; index -1 = empty), into out_val/out_idx [n_rows][k] in the same
  * order: the per-item-range lists of lg_spread_tile_resource_topk_f64 (disjoint item ranges,
  * the multi-GPU shards) give the lists
- * a single walk over all items would. k in [1, 128]. */
+ * a single walk over all items would. k in [1, 128] (lg_topk_lists_merge_wide_f64 takes k up
+ * to 1024). */
 int lg_topk_lists_merge_f64(const double *in_val, const int64_t *in_idx, int32_t n_lists,
                             int64_t n_rows, int32_t k, double *out_val, int64_t *out_idx,
                             lg_stream_t stream);
+
+/* lg_topk_lists_merge_f64 for k in [1, 1024] (same layout, order and padding; the list in
+ * LDS): merges the item-range shards' lists of a spreading run whose RECOMMEND["k"] exceeds
+ * 128 (the [:k] of model/SpreadMethod/recommend.py:31-50 over the union of the ranges). */
+int lg_topk_lists_merge_wide_f64(const double *in_val, const int64_t *in_idx, int32_t n_lists,
+                                 int64_t n_rows, int32_t k, double *out_val,
+                                 int64_t *out_idx, lg_stream_t stream);
 
 /* The tile walk: each user's F columns [item_begin, item_begin + width) are accumulated in
  * LDS (the values of the F-writing reference walk, lgcnhs_ref.h, bit for bit) and merged
@@ -425,7 +446,8 @@ int lg_topk_lists_merge_f64(const double *in_val, const int64_t *in_idx, int32_t
  * Exclusions (dropped): ex_rowptr/ex_col as in lg_rows_topk_f64 plus a per-row cursor
  * ex_cur[n_users] positioned at the walk's first item by lg_spread_tile_seek(ex_rowptr,
  * ex_col, ...) and advanced here. Walked over tiles in ascending order, the lists equal
- * lg_rows_topk_f64 over the F rows the walk sums. k in [1, 128]; dim in
+ * lg_rows_topk_f64 over the F rows the walk sums. k in [1, 128] (larger k: the host peels
+ * passes of 128, lgcnhs.ops.spread_topk_tiled); dim in
  * {32, 64, 128}. The walk keeps its stream positions in 32 bits: n_users, the interactions
  * and the exclusions must each be < 2^31; n_positions / n_ex_positions are upper bounds of
  * user_rowptr[n_users] / ex_rowptr[n_users] (the lengths of user_items / ex_col, 0 without

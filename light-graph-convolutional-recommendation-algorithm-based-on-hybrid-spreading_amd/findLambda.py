@@ -39,7 +39,8 @@ def sweep_lambdas(model, user_num: int, item_num: int, train_data_df: pd.DataFra
                   val_data_df: pd.DataFrame, test_data_df: pd.DataFrame, k: int,
                   lambdas=None, tiled: bool | None = None) -> pd.DataFrame:
     """The loop of reference :87-114 for a trained (or given) LightGCN(Opti) model: one row of
-    metrics per lambda (default 0..1 step 0.01, the reference's list)."""
+    metrics per lambda (default 0..1 step 0.01, the reference's list). k in [1, 1024] (above
+    128: ops.spread_lambda_sweep's wide dense route, or the peeled walk per lambda)."""
     if lambdas is None:
         lambdas = np.arange(0, 1 + 0.01, 0.01).tolist()
     dev = gpu_device(model.users_emb.weight)

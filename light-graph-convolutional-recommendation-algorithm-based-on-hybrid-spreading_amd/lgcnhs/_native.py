@@ -105,6 +105,10 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     ),
+    "lg_rows_topk_wide_f64": (
+        ctypes.c_int,
+        [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    ),
     "lg_hybrid_recip_f64": (ctypes.c_int, [_vp, _i64, _f64, _vp, _vp, _vp]),
     "lg_inv_degree_f64": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
     "lg_spread_group_cursor": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
@@ -119,6 +123,7 @@ SIGNATURES = {
     ),
     "lg_spread_tile_seek": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "lg_topk_lists_merge_f64": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "lg_topk_lists_merge_wide_f64": (ctypes.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "lg_spread_tile_resource_topk_lds_bytes": (_sz, [_i32, _i32, _i32]),
     "lg_spread_tile_resource_topk_f64": (
         ctypes.c_int,
@@ -160,6 +165,18 @@ _ref = None
 _lock = threading.Lock()
 
 
+def _bind(lib: ctypes.CDLL, name: str, path: str):
+    """The library's symbol `name`; a library built before the entry existed (same ABI number:
+    additions do not bump it) raises the rebuild message, not an AttributeError."""
+    try:
+        return getattr(lib, name)
+    except AttributeError:
+        raise RuntimeError(
+            f"{path} does not export {name}: it was built from older sources; rebuild it with "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950)"
+        ) from None
+
+
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     """Load (once) and type the native library; raises if it is missing."""
     global _lib
@@ -173,7 +190,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             )
         lib = ctypes.CDLL(path)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            fn = _bind(lib, name, path)
             fn.restype = res
             fn.argtypes = args
         ver = lib.lg_abi_version()
@@ -198,7 +215,7 @@ def ref_lib() -> ctypes.CDLL:
                 raise RuntimeError(f"test-reference library not found at {REF_LIB_PATH}")
             r = ctypes.CDLL(REF_LIB_PATH)
             for name, (res, args) in {**SIGNATURES, **REF_SIGNATURES}.items():
-                fn = getattr(r, name)
+                fn = _bind(r, name, REF_LIB_PATH)
                 fn.restype = res
                 fn.argtypes = args
             if r.lg_abi_version() != ABI_VERSION:

@@ -9,8 +9,10 @@ hybrid_weight    HybridS W                         model/SpreadMethod/model.py:6
 spread_resource  F = A @ W                         model/SpreadMethod/model.py:88-99
 rows_topk        argsort + filter + [:k], G * F    model/SpreadMethod/recommend.py:31-50,
                                                    model/SpreadLightGCN/model.py:151
+                 (k <= 128: K4; 128 < k <= 1024: K4w, lists in LDS, csrc/spread_wide.hip)
 spread_topk_tiled  the above over item tiles,      (same; for catalogs whose I x I W
                    never holding an I x I matrix    does not fit)
+                   (k > 128: peeled passes of 128)
 spread_recommend   dense or tiled, whichever fits  model/SpreadMethod/recommend.py:59-115
 """
 from __future__ import annotations
@@ -652,7 +654,12 @@ def spread_resource(A: Interactions, W: torch.Tensor, users: slice | None = None
 def rows_topk(F: torch.Tensor, k: int, excl: RowSets | None = None, drop: bool = True,
               eu: torch.Tensor | None = None, ei: torch.Tensor | None = None):
     """Per-row top-k of F (optionally times the fp32 score G = eu . ei), excluded columns
-    dropped (drop=True) or kept (drop=False). Returns (values fp64, indices int64, -1 pad)."""
+    dropped (drop=True) or kept (drop=False). Returns (values fp64, indices int64, -1 pad).
+    k <= 128 runs lg_rows_topk_f64 (lists sorted in registers), 128 < k <= 1024
+    lg_rows_topk_wide_f64 (same values, order and padding; lists in LDS)."""
+    k = int(k)
+    if k < 1 or k > 1024:
+        raise ValueError(f"k={k} not in [1, 1024]")
     N.require_gpu(F, "F")
     if F.dtype != torch.float64:
         raise TypeError("F must be float64")
@@ -665,11 +672,12 @@ def rows_topk(F: torch.Tensor, k: int, excl: RowSets | None = None, drop: bool =
         d = eu.shape[1]
     val = torch.empty((n, k), dtype=torch.float64, device=F.device)
     idx = torch.empty((n, k), dtype=torch.int64, device=F.device)
-    N.check(N.lib().lg_rows_topk_f64(
+    name = "lg_rows_topk_f64" if k <= 128 else "lg_rows_topk_wide_f64"
+    N.check(getattr(N.lib(), name)(
         N.ptr(F), F.stride(0), n, m, N.ptr(eu), N.ptr(ei), d,
         N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
-        N.LG_EXCL_DROP if drop else N.LG_EXCL_NONE, int(k), N.ptr(val), N.ptr(idx),
-        N.stream_handle(F.device)), "lg_rows_topk_f64")
+        N.LG_EXCL_DROP if drop else N.LG_EXCL_NONE, k, N.ptr(val), N.ptr(idx),
+        N.stream_handle(F.device)), name)
     return val, idx
 
 
@@ -1032,7 +1040,23 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     tiles and users u of sum_{i in items(u)} the pairs (P) / entries (V) of row i in the
     tile) and "w_bytes": the row bytes it gathers (one 128-byte line per (user, item) and
     tile, plus 16 bytes per overflow unit) -- extra GPU work per tile, so timed runs leave it
-    off and take the counts from tile_traffic()."""
+    off and take the counts from tile_traffic().
+
+    The walk's lists hold k <= 128 entries. 128 < k <= 1024 is served by peeling: ceil(k / 128)
+    complete walks, pass p asking for min(128, k - 128 p) entries with the items the earlier
+    passes found added to its (dropped) exclusions, its lists written to columns
+    [128 p, 128 p + its k). The walk is an exact top-k under (value desc, item asc) for any
+    exclusion set and the F it sums depends on neither k nor the exclusions, so the
+    concatenation is the exact top-k of the walk's own F and its first 128 columns are
+    bitwise the k = 128 call's. Cost: ceil(k / 128) x the k = 128 job (plus the exclusion
+    rebuilds, "t_excl_ms" in ``stats``); a pass after which every row is exhausted ends the
+    peel."""
+    k = int(k)
+    if k > 1024:
+        raise ValueError(f"k={k} not in [1, 1024]")
+    if k > PEEL_K:
+        return _spread_topk_tiled_peeled(A, lam, k, excl, drop, eu, ei, users, tile, items,
+                                         stats, count_paths, col_bounds)
     u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
     i0, i1 = (0, A.n_items) if items is None else (max(0, items.start),
                                                    min(A.n_items, items.stop))
@@ -1084,6 +1108,47 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
         stats["w_paths"] = stats.get("w_paths", 0) + int(tw.paths_read)
         stats["w_paths_hub"] = stats.get("w_paths_hub", 0) + int(tw.paths_hub)
         stats["w_bytes"] = stats.get("w_bytes", 0) + int(tw.bytes_read)
+    return vals, idxs
+
+
+PEEL_K = 128   # entries of the walk's register-sorted lists (csrc/spread_tiled.hip)
+
+
+def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets | None,
+                              drop: bool, eu, ei, users: slice | None, tile: int,
+                              items: slice | None, stats: dict | None, count_paths: bool,
+                              col_bounds: bool):
+    """spread_topk_tiled for PEEL_K < k <= 1024 (see there): passes of <= PEEL_K entries, each
+    excluding what the earlier ones found."""
+    u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
+    n = u1 - u0
+    dev = A.k_item.device
+    vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
+    idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    ex = excl if drop else None
+    n_rows = excl.n_rows if excl is not None else A.n_users
+    evs = []
+    for c0 in range(0, k, PEEL_K):
+        kp = min(PEEL_K, k - c0)
+        v, i = spread_topk_tiled(A, lam, kp, ex, True, eu, ei, users=users, tile=tile,
+                                 items=items, stats=stats, count_paths=count_paths,
+                                 col_bounds=col_bounds)
+        vals[:, c0:c0 + kp], idxs[:, c0:c0 + kp] = v, i
+        if c0 + kp >= k or not bool((i[:, kp - 1] >= 0).any()):
+            break  # (a row whose last entry is empty has no survivors left)
+        if stats is not None:
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+        hit = (i >= 0).nonzero(as_tuple=True)
+        found = RowSets.from_pairs(hit[0] + u0, i[hit], n_rows, A.n_items, dev)
+        ex = found if ex is None else RowSets.union(ex, found)
+        if stats is not None:
+            e[1].record()
+            evs.append(e)
+    if stats is not None:
+        torch.cuda.synchronize(dev)
+        stats["t_excl_ms"] = stats.get("t_excl_ms", 0.0) + sum(a.elapsed_time(b) for a, b in evs)
+        stats["peel_passes"] = stats.get("peel_passes", 0) + c0 // PEEL_K + 1
     return vals, idxs
 
 
@@ -1246,9 +1311,11 @@ def spread_lambda_sweep(A: Interactions, lams, k: int, excl: RowSets | None,
              half the free memory); per lambda only the HybridScale (ra per interaction, rb
              per item) changes and the score bounds are recomputed (cheap; the per-column
              bounds of every tile would not fit). If the cache does not fit, each lambda
-             rebuilds the tiles.
+             rebuilds the tiles. At k > 128 the tiled route calls spread_topk_tiled per
+             lambda (its peeled passes; no shared TileWalk, no tile cache).
     Every result is bitwise the one spread_recommend(A, lam, ...) returns."""
     lams = [float(x) for x in lams]
+    k = int(k)
     dev = A.k_item.device
     if tiled is None:
         tiled = not dense_spread_fits(A.n_items, dev)
@@ -1258,6 +1325,11 @@ def spread_lambda_sweep(A: Interactions, lams, k: int, excl: RowSets | None,
             W = hybrid_weight(gW, A.k_item, lam)
             v, i = spread_topk(A, W, k, excl, drop, eu, ei)
             del W
+            yield lam, v, i
+        return
+    if k > PEEL_K:
+        for lam in lams:
+            v, i = spread_topk_tiled(A, lam, k, excl, drop, eu, ei, tile=tile)
             yield lam, v, i
         return
     if cache_bytes is None:
@@ -1295,18 +1367,21 @@ def spread_lambda_sweep(A: Interactions, lams, k: int, excl: RowSets | None,
 
 def merge_topk_lists(vals: torch.Tensor, idxs: torch.Tensor):
     """[L, n, k] sorted lists (index -1 = empty) -> the [n, k] top-k of their union, same
-    order (value desc, index asc)."""
+    order (value desc, index asc). k <= 128: lg_topk_lists_merge_f64; 128 < k <= 1024:
+    lg_topk_lists_merge_wide_f64 (the list in LDS)."""
     N.require_gpu(vals, "vals")
     if vals.dtype != torch.float64 or idxs.dtype != torch.int64 or vals.shape != idxs.shape \
             or vals.dim() != 3:
         raise ValueError("merge_topk_lists: vals fp64 / idxs int64 of one [L, n, k] shape")
     L, n, k = vals.shape
+    if k < 1 or k > 1024:
+        raise ValueError(f"merge_topk_lists: k={k} not in [1, 1024]")
     vals, idxs = vals.contiguous(), idxs.contiguous()
     ov = torch.empty((n, k), dtype=torch.float64, device=vals.device)
     oi = torch.empty((n, k), dtype=torch.int64, device=vals.device)
-    N.check(N.lib().lg_topk_lists_merge_f64(N.ptr(vals), N.ptr(idxs), L, n, k, N.ptr(ov),
-                                            N.ptr(oi), N.stream_handle(vals.device)),
-            "lg_topk_lists_merge_f64")
+    name = "lg_topk_lists_merge_f64" if k <= 128 else "lg_topk_lists_merge_wide_f64"
+    N.check(getattr(N.lib(), name)(N.ptr(vals), N.ptr(idxs), L, n, k, N.ptr(ov), N.ptr(oi),
+                                   N.stream_handle(vals.device)), name)
     return ov, oi
 
 

@@ -3,9 +3,11 @@ model/LightGCN/evaluation.py:17-86), called from the periodic-eval block of the 
 loop (reference model/LightGCN/train.py:147-180, here model/LightGCN/train.py).
 
 getValRecommendations scores with the layer-0 embeddings, masks the TRAIN positives only
-with -1024 and takes the top-k (reference :30-52) in one HIP kernel
-(lg_score_topk_screened_f32, lists bit for bit lg_score_topk_f32's; ties ordered by (score
-desc, item asc); 128 < k <= 1024: lg_score_topk_wide_f32, the same lists from global slabs);
+with -1024 and takes the top-k (reference :30-52) in one HIP kernel, chosen by
+ops.score_topk's dispatch (lg_score_topk_screened_f32 above ops.screen_pays' size crossover,
+lg_score_topk_f32 below it -- the ML-100K / ML-1M evaluations --, lists bit for bit the
+same; 128 < k <= 1024: lg_score_topk_wide_f32, the same lists from global slabs; ties ordered
+by (score desc, item asc));
 the val adjacency is accepted and unused, as in
 the reference (it converts it at :38 and never reads it). calValLoss runs the forward on the
 val adjacency (HIP propagation), draws one negative per val edge (structured negative

@@ -2,11 +2,13 @@
 (reference model/LightGCN/recommend.py:22-159).
 
 recommendForAllUser scores with the layer-0 embeddings, masks train and val positives with
--1024 and takes the top-k — in one HIP kernel (lg_score_topk_screened_f32: a bf16 MFMA
-screen, the exact fp32 chain of lg_score_topk_f32 on the tiles it cannot rule out, the same
-lists bit for bit) that never holds the U x I score matrix; ties are ordered (score desc,
-item asc). RECOMMEND["k"] up to 128 takes that kernel; 128 < k <= 1024 takes
-lg_score_topk_wide_f32 (the same scores and order, lists in global slabs); larger k raises.
+-1024 and takes the top-k — in one HIP kernel that never holds the U x I score matrix,
+chosen by ops.score_topk's dispatch: above ops.screen_pays' size crossover
+lg_score_topk_screened_f32 (a bf16 MFMA screen, the exact fp32 chain of lg_score_topk_f32 on
+the tiles it cannot rule out), below it lg_score_topk_f32 itself; the lists are the same bit
+for bit, ties ordered (score desc, item asc). RECOMMEND["k"] up to 128 takes those kernels;
+128 < k <= 1024 takes lg_score_topk_wide_f32 (the same scores and order, lists in global
+slabs); larger k raises.
 """
 import numpy as np
 import pandas as pd

@@ -27,7 +27,9 @@ def _save(recs: dict) -> None:
 
 def recommendForAllUser(F_new: np.ndarray, user_num: int, train_data_df: pd.DataFrame,
                         val_data_df: pd.DataFrame, k: int) -> dict:
-    """Top-k by F_new without train|val items (reference :18-52)."""
+    """Top-k by F_new without train|val items (reference :18-52). k in [1, 1024]:
+    lg_rows_topk_f64 up to 128, lg_rows_topk_wide_f64 above (the reference's [:k] takes any
+    k; larger k raises ValueError)."""
     dev = gpu_device()
     F = torch.as_tensor(np.ascontiguousarray(F_new[:user_num]), dtype=torch.float64).to(dev)
     excl = exclusion_from_dfs(user_num, F.shape[1], train_data_df, val_data_df, device=dev)
@@ -40,7 +42,9 @@ def recommendForAllUser(F_new: np.ndarray, user_num: int, train_data_df: pd.Data
 def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.DataFrame,
                          val_data_df: pd.DataFrame, lambda_val: float, k: int, device=None,
                          tiled: bool | None = None):
-    """Device (values fp64, items int64) of the whole LGCNHS recommendation."""
+    """Device (values fp64, items int64) of the whole LGCNHS recommendation. k in [1, 1024];
+    above 128 the dense path takes lg_rows_topk_wide_f64 and the tiled path peels
+    ceil(k / 128) walks (ops.spread_topk_tiled)."""
     dev = device or gpu_device(model.users_emb.weight)
     both = pd.concat([train_data_df, val_data_df])
     inter = ops.Interactions.from_pairs(

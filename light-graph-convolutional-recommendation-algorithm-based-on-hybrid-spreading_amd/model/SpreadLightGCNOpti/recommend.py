@@ -1,6 +1,6 @@
 """LGCNHS recommendation with the reference's interface
 (reference model/SpreadLightGCNOpti/recommend.py:18-79), fused on the GPU as
-model.SpreadLightGCN.recommend.spread_lightgcn_topk."""
+model.SpreadLightGCN.recommend.spread_lightgcn_topk (RECOMMEND["k"] in [1, 1024], as there)."""
 import pandas as pd
 
 from const import cfg

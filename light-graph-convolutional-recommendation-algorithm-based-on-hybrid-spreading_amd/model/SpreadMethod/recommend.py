@@ -33,7 +33,9 @@ def _to_dict(idx: torch.Tensor, user_num: int) -> dict:
 
 def recommendForAllUser(F_new: np.ndarray, user_num: int, train_data_df: pd.DataFrame,
                         val_data_df: pd.DataFrame, k: int) -> dict:
-    """Per user: the k best items by F_new not in train|val (reference :18-56)."""
+    """Per user: the k best items by F_new not in train|val (reference :18-56). k in
+    [1, 1024]: lg_rows_topk_f64 up to 128, lg_rows_topk_wide_f64 above (the reference's [:k]
+    takes any k; larger k raises ValueError)."""
     dev = gpu_device()
     F = torch.as_tensor(np.ascontiguousarray(F_new[:user_num]), dtype=torch.float64).to(dev)
     excl = exclusion_from_dfs(user_num, F.shape[1], train_data_df, val_data_df, device=dev)
@@ -47,7 +49,9 @@ def spread_method_topk(user_num: int, item_num: int, train_data_df: pd.DataFrame
                        val_data_df: pd.DataFrame, method: str, lambda_val: float,
                        dataset: str, k: int, unfiltered: bool = False, device=None,
                        tiled: bool | None = None):
-    """Device (values, items) of the whole spreading recommendation."""
+    """Device (values, items) of the whole spreading recommendation. k in [1, 1024]; above
+    128 the dense path takes lg_rows_topk_wide_f64 and the tiled path peels ceil(k / 128)
+    walks (ops.spread_topk_tiled)."""
     dev = device or gpu_device()
     both = pd.concat([train_data_df, val_data_df])
     inter = ops.Interactions.from_pairs(
