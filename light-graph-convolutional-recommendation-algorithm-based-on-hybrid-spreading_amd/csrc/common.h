@@ -91,6 +91,46 @@ __device__ __forceinline__ void wave_bitonic_sort(K (&k)[M], int (&id)[M]) {
   }
 }
 
+// The bitonic stages (block size `size`; stride = S0, S0 / 2, .. 1, S0 < 64*M) over 64*M
+// elements held as k[j], id[j]: entry j of a lane is element e = base + j*64 + lane (base a
+// multiple of 64*M: the registers are one chunk of a longer sequence). wave_bitonic_sort's
+// stage body; that keeps its own text, which the ring kernel's code was measured on.
+template <typename K, int M, int S0>
+__device__ __forceinline__ void wave_bitonic_stages(K (&k)[M], int (&id)[M], int base, int size) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int stride = S0; stride > 0; stride >>= 1) {
+    if (stride >= 64) {
+      const int js = stride / 64;
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        if (j & js) continue;
+        const int e = base + j * 64 + lane;     // lower element of the pair
+        const bool desc = (e & size) == 0;      // this block sorts best-first
+        const int p = j | js;
+        const bool lo_better = before(k[j], id[j], k[p], id[p]);
+        if (lo_better != desc) {
+          K tk = k[j]; k[j] = k[p]; k[p] = tk;
+          int ti = id[j]; id[j] = id[p]; id[p] = ti;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        const int e = base + j * 64 + lane;
+        const K ok = __shfl_xor(k[j], stride);
+        const int oi = __shfl_xor(id[j], stride);
+        const bool lower = (e & stride) == 0;
+        const bool desc = (e & size) == 0;
+        const bool mine_better = before(k[j], id[j], ok, oi);
+        // lower slot of a best-first block keeps the better one, etc.
+        const bool keep_mine = (lower == desc) ? mine_better : !mine_better;
+        if (!keep_mine) { k[j] = ok; id[j] = oi; }
+      }
+    }
+  }
+}
+
 // Compact a wave-owned LDS candidate list (n valid entries, capacity CAP = 64*M) down to
 // its best `keep` entries, written back sorted at [0, keep). Returns the new count and sets
 // `tau` to the key of the last kept entry when the list is full (count == keep), else -inf

@@ -1,20 +1,17 @@
-// K3/K4: hybrid spreading (mass diffusion / heat conduction mix) in fp64, gfx950.
+// K3: hybrid spreading (mass diffusion / heat conduction mix) in fp64, gfx950.
 //
 // Reference (model/SpreadMethod/model.py), all dense numpy fp64 on the host:
 //   getSpreadingGeneralMat :14-27   k_u = A.sum(1) (0 -> 1); general_W = (A.T / k_u) @ A
 //   HybridS                :63-85   k_i = A.sum(0); den = k_i^(1-l) (x) k_j^l; den==0 -> 1;
 //                                    W = general_W / den
 //   getResource            :88-99   F = A @ W
-//   recommendForAllUser    model/SpreadMethod/recommend.py:31-50: per user
-//                                    argsort(F[u])[::-1], drop train|val items, [:k]
-//   G * F                  model/SpreadLightGCN/model.py:151 (fp32 G promoted to fp64)
 //
 // A is 0/1 and sparse, so the GEMMs are replaced by sparse row sums with a deterministic
 // ascending summation order:
 //   general_W[i][j] = sum_{v in users(i)} [j in items(v)] * fl(1/k_v)   (one block per i)
 //   F[u][j]         = sum_{i in items(u)} W[i][j]                        (one block per u)
-// which cost E*avg_deg and E*I instead of 2*U*I^2 each. Top-K over the dense rows is the
-// candidate-list selection of common.h, one wave per row, 64 columns per step.
+// which cost E*avg_deg and E*I instead of 2*U*I^2 each. The top-K over the rows of F (K4) is
+// rows_topk.hip.
 #include "common.h"
 
 namespace lg {
@@ -187,165 +184,6 @@ __global__ __launch_bounds__(256) void k_spread_resource(
   F[u * ldf + j] = s;
 }
 
-// fp32 score in the chain order of lg_score_topk_f32 (see topk.hip header).
-template <int D>
-__device__ __forceinline__ float chain_score(const float *__restrict__ us,
-                                             const float *__restrict__ it) {
-  constexpr int Q = D / 4;
-  float r[D];
-  const float4 *p4 = reinterpret_cast<const float4 *>(it);
-#pragma unroll
-  for (int t = 0; t < D / 4; ++t) {
-    const float4 q = p4[t];
-    r[4 * t] = q.x;
-    r[4 * t + 1] = q.y;
-    r[4 * t + 2] = q.z;
-    r[4 * t + 3] = q.w;
-  }
-  float acc = 0.f;
-#pragma unroll
-  for (int s = 0; s < Q; ++s)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) acc = __builtin_fmaf(us[g * Q + s], r[g * Q + s], acc);
-  return acc;
-}
-
-// NW waves per row (one row per block), D == 0: no G factor. Wave w scans the row's w-th
-// column range (whole 64-column steps) in ascending order into its own candidate list --
-// at the C3 Douban shape (600 rows x 20,000 columns) one wave per row left the chip mostly
-// idle behind each step's load -> 64-FMA chain latency -- then the waves' top-k lists merge
-// pairwise in log2(NW) rounds (each merge: the partner's <= k entries appended, the list
-// compacted; the (value desc, column asc) order is total, so the result is the single
-// scan's). Columns arrive in ascending order within a wave, so a tie with tau loses.
-template <int M, int D, int NW>
-__global__ __launch_bounds__(64 * NW) void k_rows_topk(
-    const double *__restrict__ F, int64_t ldf, int64_t n_rows, int64_t n_cols,
-    const float *__restrict__ eu, const float *__restrict__ ei,
-    const int64_t *__restrict__ ex_rowptr, const int32_t *__restrict__ ex_col, int excl_mode,
-    int k, double *__restrict__ out_val, int64_t *__restrict__ out_idx) {
-  constexpr int CAP = 64 * M;
-  constexpr int DU = D > 0 ? D : 1;
-  static_assert(CAP >= 128 && (NW & (NW - 1)) == 0, "a merge holds two lists of k <= CAP / 2");
-  __shared__ double cs[NW][CAP];
-  __shared__ int ci[NW][CAP];
-  __shared__ float us[DU];
-  __shared__ int s_n[NW];
-  const int wave = threadIdx.x / 64;
-  const int lane = lane_id();
-  const int64_t r = blockIdx.x;  // (< n_rows: one block per row)
-  if (D > 0) {
-    for (int t = threadIdx.x; t < D; t += 64 * NW) us[t] = eu[r * D + t];
-    __syncthreads();
-  }
-  int64_t lo = 0, hi = 0;
-  if (ex_rowptr && excl_mode == LG_EXCL_DROP) {
-    lo = ex_rowptr[r];
-    hi = ex_rowptr[r + 1];
-  }
-  const int64_t span = ((n_cols + NW - 1) / NW + 63) / 64 * 64;
-  const int64_t c0 = wave * span, c1 = c0 + span < n_cols ? c0 + span : n_cols;
-  int cnt = 0;
-  double tau = neg_inf<double>();
-  int tau_id = kPadId;
-  const double *row = F + r * ldf;
-  // no G: two 64-column steps per round (both loads in flight; the candidates of the first
-  // step are taken before the second's, so columns still reach the list in ascending order):
-  // 0.141 -> 0.119 ms at the C3 shape. With G one step: two interleaved score chains measured
-  // slower (0.52 -> 0.59 ms: 186 instead of 125 VGPRs, half the waves per SIMD)
-  constexpr int STEPS = D > 0 ? 1 : 2;
-  for (int64_t j00 = c0; j00 < c1; j00 += 64 * STEPS) {
-    double v2[STEPS];
-#pragma unroll
-    for (int h = 0; h < STEPS; ++h) {
-      const int64_t j = j00 + 64 * h + lane;
-      v2[h] = j < c1 ? row[j] : neg_inf<double>();
-    }
-    if constexpr (D > 0) {
-      if (j00 + lane < c1) v2[0] = (double)chain_score<DU>(us, ei + (j00 + lane) * D) * v2[0];
-    }
-#pragma unroll
-    for (int h = 0; h < STEPS; ++h) {
-      const int64_t j0 = j00 + 64 * h;
-      if (j0 >= c1) break;  // (wave-uniform)
-      const int64_t j = j0 + lane;
-      const bool valid = j < c1;
-      const double v = v2[h];
-      bool cand = valid && v > tau;
-      if (__ballot(cand)) {
-        if (cand && lo < hi) {
-          const int64_t p = lower_bound_i32(ex_col, lo, hi, (int32_t)j);
-          lo = p;
-          if (p < hi && ex_col[p] == (int32_t)j) cand = false;
-        }
-        const uint64_t bal = __ballot(cand);
-        const int pos = cnt + __popcll(bal & lanemask_lt());
-        if (cand) {
-          cs[wave][pos] = v;
-          ci[wave][pos] = (int)j;
-        }
-        cnt += __popcll(bal);
-        if (cnt > CAP - 64) {
-          wave_sync();
-          cnt = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-        }
-      }
-    }
-  }
-  wave_sync();
-  int nc = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-  if (lane == 0) s_n[wave] = nc;
-#pragma unroll
-  for (int st = 1; st < NW; st <<= 1) {
-    __syncthreads();
-    if (wave % (2 * st) == 0) {  // (wave + st < NW: NW is a power of two)
-      const int n1 = s_n[wave + st];
-      for (int e = lane; e < n1; e += 64) {
-        cs[wave][nc + e] = cs[wave + st][e];
-        ci[wave][nc + e] = ci[wave + st][e];
-      }
-      wave_sync();
-      nc = wave_compact<double, M>(cs[wave], ci[wave], nc + n1, k, tau, tau_id);
-      if (lane == 0) s_n[wave] = nc;
-    }
-  }
-  if (wave == 0) {
-    for (int e = lane; e < k; e += 64) {
-      out_val[r * k + e] = e < nc ? cs[0][e] : neg_inf<double>();
-      out_idx[r * k + e] = e < nc ? ci[0][e] : -1;
-    }
-  }
-}
-
-// rows of at least this many columns get 8 waves each, shorter ones one
-constexpr int64_t kRowsSplitCols = 4096;
-
-template <int M, int NW>
-static void launch_rows_topk_nw(int dim, const double *F, int64_t ldf, int64_t n_rows,
-                                int64_t n_cols, const float *eu, const float *ei,
-                                const int64_t *ex_rowptr, const int32_t *ex_col, int excl_mode,
-                                int k, double *out_val, int64_t *out_idx, hipStream_t s) {
-  dim3 grid((unsigned)n_rows), block(64 * NW);
-  switch (eu ? dim : 0) {
-    case 0: k_rows_topk<M, 0, NW><<<grid, block, 0, s>>>(F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k, out_val, out_idx); break;
-    case 32: k_rows_topk<M, 32, NW><<<grid, block, 0, s>>>(F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k, out_val, out_idx); break;
-    case 64: k_rows_topk<M, 64, NW><<<grid, block, 0, s>>>(F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k, out_val, out_idx); break;
-    default: k_rows_topk<M, 128, NW><<<grid, block, 0, s>>>(F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k, out_val, out_idx); break;
-  }
-}
-
-template <int M>
-static void launch_rows_topk(int dim, const double *F, int64_t ldf, int64_t n_rows,
-                             int64_t n_cols, const float *eu, const float *ei,
-                             const int64_t *ex_rowptr, const int32_t *ex_col, int excl_mode,
-                             int k, double *out_val, int64_t *out_idx, hipStream_t s) {
-  if (n_cols >= kRowsSplitCols)
-    launch_rows_topk_nw<M, 8>(dim, F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode,
-                              k, out_val, out_idx, s);
-  else
-    launch_rows_topk_nw<M, 1>(dim, F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode,
-                              k, out_val, out_idx, s);
-}
-
 }  // namespace lg
 
 using namespace lg;
@@ -429,32 +267,4 @@ extern "C" int lg_spread_resource_f64(const int64_t *user_rowptr, const int32_t 
                         s>>>(user_rowptr + u0, user_items, W, n_items, F + u0 * ldf, ldf);
   }
   return launch_status("lg_spread_resource_f64");
-}
-
-extern "C" int lg_rows_topk_f64(const double *F, int64_t ldf, int64_t n_rows,
-                                int64_t n_cols, const float *eu, const float *ei,
-                                int32_t dim, const int64_t *ex_rowptr,
-                                const int32_t *ex_col, int32_t excl_mode, int32_t k,
-                                double *out_val, int64_t *out_idx, lg_stream_t stream) {
-  LG_REQUIRE(F && out_val && out_idx && n_rows >= 0 && n_cols >= 0 && ldf >= n_cols &&
-                 n_cols < 0x7fffffff,
-             "lg_rows_topk_f64: bad arguments");
-  LG_REQUIRE(k >= 1 && k <= 128, "lg_rows_topk_f64: k=%d not in [1,128]", k);
-  LG_REQUIRE(!eu == !ei, "lg_rows_topk_f64: eu/ei must both be set or both NULL");
-  LG_REQUIRE(!eu || dim == 32 || dim == 64 || dim == 128,
-             "lg_rows_topk_f64: dim %d not in {32,64,128}", dim);
-  LG_REQUIRE(excl_mode == LG_EXCL_DROP || excl_mode == LG_EXCL_NONE,
-             "lg_rows_topk_f64: bad excl_mode %d", excl_mode);
-  LG_REQUIRE(!ex_rowptr == !ex_col, "lg_rows_topk_f64: ex_rowptr/ex_col must both be set");
-  LG_REQUIRE(!(eu && excl_mode == LG_EXCL_NONE && ex_rowptr),
-             "lg_rows_topk_f64: a G factor with exclusions requires LG_EXCL_DROP");
-  if (n_rows == 0) return LG_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (k <= 64)
-    launch_rows_topk<2>(dim, F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k,
-                        out_val, out_idx, s);
-  else
-    launch_rows_topk<4>(dim, F, ldf, n_rows, n_cols, eu, ei, ex_rowptr, ex_col, excl_mode, k,
-                        out_val, out_idx, s);
-  return launch_status("lg_rows_topk_f64");
 }

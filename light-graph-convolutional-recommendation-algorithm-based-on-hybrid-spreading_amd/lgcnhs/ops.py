@@ -9,7 +9,7 @@ hybrid_weight    HybridS W                         model/SpreadMethod/model.py:6
 spread_resource  F = A @ W                         model/SpreadMethod/model.py:88-99
 rows_topk        argsort + filter + [:k], G * F    model/SpreadMethod/recommend.py:31-50,
                                                    model/SpreadLightGCN/model.py:151
-                 (k <= 128: K4; 128 < k <= 1024: K4w, lists in LDS, csrc/spread_wide.hip)
+                 (k <= 128: K4; 128 < k <= 1024: lists in LDS; csrc/rows_topk.hip)
 spread_topk_tiled  the above over item tiles,      (same; for catalogs whose I x I W
                    never holding an I x I matrix    does not fit)
                    (k > 128: peeled passes of 128)

@@ -1,4 +1,4 @@
-"""Measure the spreading top-K for 128 < k <= 1024 (csrc/spread_wide.hip and the peeled tile
+"""Measure the spreading top-K for 128 < k <= 1024 (csrc/rows_topk.hip and the peeled tile
 walk of ops.spread_topk_tiled) and write profiles/spread_wide.json.
 
 dense   bench.py's Douban stand-in (600 users x 20,000 items, 60,000 Zipf(1.1) interactions,
@@ -13,7 +13,7 @@ tiled   bench.py's c4 graph (200,000 x 200,000, 20M interactions, d = 64, tile 2
         seconds, the ratio to k = 128 and the share spent rebuilding exclusions between the
         peeled passes (stats["t_excl_ms"]).
 --resources FILE merges the compiler's per-kernel report (hipcc
--Rpass-analysis=kernel-resource-usage on csrc/spread_wide.hip, stderr saved to FILE) into
+-Rpass-analysis=kernel-resource-usage on csrc/rows_topk.hip, stderr saved to FILE) into
 the JSON: VGPRs, LDS bytes, scratch bytes per instantiation. No GPU needed for that step.
 
 Usage: python scripts/spread_wide_time.py [--skip-tiled] [--out profiles/spread_wide.json]
@@ -46,11 +46,16 @@ def parse_resources(path):
     res = {}
     for blk in open(path).read().split("Function Name: ")[1:]:
         name = blk.split()[0].rstrip("]")
-        m = re.match(r"_ZN2lg\d+(k_rows_topk_wide|k_lists_merge_wide)I((?:Li\d+E)+)", name)
-        if not m:
+        # k_rows_topk<lg::LdsList<H>, D, NW> (the register-sorted RegList<M> instantiations are
+        # the k <= 128 entry's) and k_lists_merge_wide<CAP, NWB>
+        m = re.match(r"_ZN2lg\d+(k_rows_topk|k_lists_merge_wide)I(?:NS_7LdsListI)?((?:Li\d+E)+)", name)
+        if not m or (m.group(1) == "k_rows_topk") != ("LdsList" in name):
             continue
-        args = [int(x) for x in re.findall(r"Li(\d+)E", m.group(2))]
-        key = f"{m.group(1)}<{', '.join(map(str, args))}>"
+        args = [int(x) for x in re.findall(r"Li(\d+)E", name.split("EEv")[0])]
+        if m.group(1) == "k_rows_topk":
+            key = f"k_rows_topk<LdsList<{args[0]}>, {args[1]}, {args[2]}>"
+        else:
+            key = f"k_lists_merge_wide<{', '.join(map(str, args))}>"
 
         def field(label):
             return int(re.search(re.escape(label) + r": (\d+)", blk).group(1))
@@ -63,7 +68,8 @@ def parse_resources(path):
 if a.resources:
     out["resources"] = {
         "source": "hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage, "
-                  "csrc/spread_wide.hip; k_rows_topk_wide<CAP, D, waves per row>, "
+                  "csrc/rows_topk.hip; k_rows_topk<LdsList<H>, D, waves per row> (CAP = 2 H; the record of "
+                  "k_rows_topk_wide<CAP, D, waves per row> is the same class), "
                   "k_lists_merge_wide<CAP, rows per block>",
         "kernels": parse_resources(a.resources)}
     assert all(v["scratch_bytes_per_lane"] == 0 for v in out["resources"]["kernels"].values())

@@ -80,6 +80,31 @@ def test_hybrid_transpose_and_rows_topk_exact():
     np.testing.assert_array_equal(v.cpu().numpy(), ov)
 
 
+@pytest.mark.parametrize("k", [64, 128])
+@pytest.mark.parametrize("d", [32, 64, 128])
+def test_rows_topk_G_factor_classes(d, k):
+    """lg_rows_topk_f64 with the G factor at every embedding width and both list classes
+    (k <= 64, k <= 128), eight waves per row (12 x 5001: ties across the waves' ranges, one
+    constant row, a last step of one column) and one (40 x 300): indices and value bits of
+    the oracle's selection over chain score x F."""
+    from lgcnhs import ops
+    from lgcnhs.graph import RowSets
+    rng = np.random.default_rng(11 + d)
+    for (U, I, q, n_ex) in ((12, 5001, 4, 3000), (40, 300, 8, 900)):
+        F = np.round(rng.random((U, I)) * q) / q
+        if U == 12:
+            F[3, :] = 0.5
+        rp, col = O.exclusion_csr(U, I, (rng.integers(0, U, n_ex), rng.integers(0, I, n_ex)))
+        ex = RowSets(torch.as_tensor(rp).to(DEV), torch.as_tensor(col).to(DEV), U, I)
+        eu = (rng.standard_normal((U, d)) * 0.1).astype(np.float32)
+        ei = (rng.standard_normal((I, d)) * 0.1).astype(np.float32)
+        v, i = ops.rows_topk(torch.as_tensor(F).to(DEV), k, ex, drop=True,
+                             eu=torch.as_tensor(eu).to(DEV), ei=torch.as_tensor(ei).to(DEV))
+        ov, oi = O.rows_topk(O.chain_scores(eu, ei).astype(np.float64) * F, k, rp, col)
+        np.testing.assert_array_equal(i.cpu().numpy(), oi)
+        np.testing.assert_array_equal(v.cpu().numpy().view(np.int64), ov.view(np.int64))
+
+
 @pytest.mark.parametrize("tag", ["hybrid", "hybrid85", "probs_ml", "heats_db"])
 def test_recommend_spread_method_vs_reference(golden, tag):
     import pandas as pd
