@@ -255,6 +255,29 @@ int lg_score_topk_wide_f32(const float *eu, const float *ei, int64_t n_users, in
                            float mask_value, int32_t k, int32_t n_splits, float *out_val,
                            int64_t *out_idx, void *ws, size_t ws_bytes, lg_stream_t stream);
 
+/* lg_score_topk_f32 for a short list of users (csrc/topk_batch.hip K2b): the request form of
+ * model/LightGCN/recommend.py:83-114 -- the top-k of n_batch <= 64 rows user_ids[b] of the
+ * full user table, without gathering embedding or exclusion rows. Row b of the outputs equals
+ * lg_score_topk_f32's row user_ids[b] bit for bit (score chain, mask, strict admission, order,
+ * padding). user_ids (device, int64) may repeat and need not be sorted; NULL means
+ * 0 .. n_batch-1. ex_rowptr / ex_col are the FULL table's exclusion CSR (n_table_users + 1
+ * row pointers), indexed by user id. An id outside [0, n_table_users) reads no table row of
+ * its own (the index is clamped) and its output row is padding. k in [1, 128], dim in
+ * {32, 64, 128}, n_items < 2^31 - 1. The items are divided over every wave of a grid that
+ * fills the device; the workspace holds one partial list per (workgroup, user):
+ * lg_score_topk_batch_ws_bytes, which does not depend on the device (0 for arguments the call
+ * refuses). */
+size_t lg_score_topk_batch_ws_bytes(int64_t n_batch, int64_t n_items, int32_t dim, int32_t k);
+/* model/LightGCN/recommend.py:83-114 for the users of one request (above). LG_ERR_ARG on a
+ * null pointer, n_batch outside [1, 64], bad dim or k, a half-set exclusion pair;
+ * LG_ERR_WORKSPACE when ws is NULL or short; all before any launch. Never allocates, never
+ * syncs. */
+int lg_score_topk_batch_f32(const float *eu, const float *ei, const int64_t *user_ids,
+                            int64_t n_batch, int64_t n_table_users, int64_t n_items, int32_t dim,
+                            const int64_t *ex_rowptr, const int32_t *ex_col, float mask_value,
+                            int32_t k, float *out_val, int64_t *out_idx, void *ws,
+                            size_t ws_bytes, lg_stream_t stream);
+
 /* Dense masked score matrix G[u][i] (same score definition and mask as above), written
  * with leading dimension ldg. Replaces getAllocateMat's matmul + masks
  * (model/SpreadLightGCN/model.py:74-104, model/SpreadLightGCNOpti/model.py:139-169). */

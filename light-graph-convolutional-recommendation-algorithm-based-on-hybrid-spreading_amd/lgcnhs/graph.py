@@ -229,6 +229,23 @@ class RowSets:
         """Rows [r0, r1) keeping absolute offsets into ``col`` (no copy of col)."""
         return RowSets(self.rowptr[r0:r1 + 1], self.col, r1 - r0, self.n_cols)
 
+    def take(self, rows, return_index: bool = False):
+        """The CSR of the given rows in the given order (duplicates allowed): row j of the
+        result is row rows[j] of this one (a copy of those rows' columns). With return_index
+        also the position in ``self.col`` of every entry of the result (to gather arrays
+        aligned with ``col``)."""
+        dev = self.rowptr.device
+        r = torch.as_tensor(rows).to(dev, torch.int64).reshape(-1)
+        n = int(r.numel())
+        deg = self.rowptr[r + 1] - self.rowptr[r]
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(deg, 0, out=rowptr[1:])
+        # entry e of new row j comes from rowptr[rows[j]] + (e - new rowptr[j])
+        src = torch.repeat_interleave(self.rowptr[r] - rowptr[:-1], deg) \
+            + torch.arange(int(rowptr[-1]) if n else 0, device=dev)
+        out = RowSets(rowptr, self.col[src], n, self.n_cols)
+        return (out, src) if return_index else out
+
 
 _ADJ_CACHE: dict = {}
 

@@ -566,6 +566,84 @@ def _score_topk_wide(eu, ei, k: int, excl, mask_value: float, n_splits):
     return val, idx
 
 
+BATCH_CALL_USERS = 64  # users per lg_score_topk_batch_f32 call (csrc/topk_batch.hip)
+BATCH_K_MAX = 128      # its largest k
+# score_topk_users sends lists of up to this many users to lg_score_topk_batch_f32 (in chunks
+# of BATCH_CALL_USERS) and longer ones to score_topk on gathered rows. Set from
+# profiles/topk_batch.json (scripts/topk_batch_time.py): the largest B at which the batch
+# kernel beats score_topk's best configuration (default dispatch or screen=False at 64 .. 4096
+# splits, rows gathered outside the timing) by more than the spread at 100K and 1M items, every
+# k and d timed: 0.38-0.88 of its time at B <= 16; at B = 32 it wins at k = 20 (0.60-0.74) and
+# loses at k = 100 (1.12-1.42), at B >= 64 it loses everywhere (1.16-8.0).
+BATCH_MAX_USERS = 16
+
+
+def batch_topk_grid(n_batch: int, n_items: int, k: int, device) -> tuple:
+    """(workgroups, waves per workgroup, items per wave) of lg_score_topk_batch_f32's scoring
+    launch (the host code of csrc/topk_batch.hip, restated): every wave holds all n_batch users
+    and scores items_per_wave consecutive items."""
+    ng = 1 if n_batch <= 16 else (2 if n_batch <= 32 else 4)
+    m = 1 if k <= 32 else (2 if k <= 64 else 4)
+    waves = 1 if ng * m >= 16 else (2 if ng * m >= 8 else 4)
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    tiles = (n_items + 15) // 16
+    blocks = min(512, cus * (2 if waves * ng * m <= 8 else 1), -(-tiles // waves))
+    ipw = -(-tiles // (blocks * waves)) * 16
+    busy = -(-n_items // ipw)  # waves with items
+    return -(-busy // waves), waves, ipw
+
+
+def _user_ids(users, n_users: int, device) -> torch.Tensor:
+    """An int64 device tensor of user ids; a list or a CPU tensor is validated on the host
+    (a device tensor is taken as it is: no sync)."""
+    t = torch.as_tensor(users)
+    if t.numel() and (t.dtype == torch.bool or t.is_floating_point()):
+        raise ValueError("user ids must be integers")
+    t = t.reshape(-1).to(torch.int64)
+    if not t.is_cuda:
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n_users):
+            raise ValueError(f"user id outside [0, {n_users})")
+        t = t.to(device)
+    return t.contiguous()
+
+
+def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
+                     excl: RowSets | None = None, mask_value: float = MASK_VALUE):
+    """Top-k items for the given users only: (values fp32 [B, k], indices int64 [B, k]), row j
+    = score_topk's row users[j] of the full tables bit for bit. users: a list or tensor of ids
+    into eu and excl (any order, duplicates allowed); a list or CPU tensor is checked on the
+    host (ValueError on a bad id). Up to BATCH_MAX_USERS users (k <= 128) run
+    lg_score_topk_batch_f32 in chunks of 64 -- no embedding or exclusion rows are gathered;
+    longer lists and 128 < k <= 1024 run score_topk on the gathered rows."""
+    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    nu, d = eu.shape
+    ni = ei.shape[0]
+    k = int(k)
+    if ei.shape[1] != d:
+        raise ValueError("eu/ei dims differ")
+    if excl is not None and excl.n_rows != nu:
+        raise ValueError(f"exclusion rows {excl.n_rows} != users {nu}")
+    ids = _user_ids(users, nu, eu.device)
+    nb = int(ids.numel())
+    if nb == 0 or nb > BATCH_MAX_USERS or k > BATCH_K_MAX:
+        return score_topk(eu[ids], ei, k, excl.take(ids) if excl is not None else None,
+                          mask_value)
+    if k < 1:
+        raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
+    val = torch.empty((nb, k), dtype=torch.float32, device=eu.device)
+    idx = torch.empty((nb, k), dtype=torch.int64, device=eu.device)
+    ws_bytes = N.lib().lg_score_topk_batch_ws_bytes(min(nb, BATCH_CALL_USERS), ni, d, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=eu.device)
+    for b0 in range(0, nb, BATCH_CALL_USERS):
+        b1 = min(nb, b0 + BATCH_CALL_USERS)
+        N.check(N.lib().lg_score_topk_batch_f32(
+            N.ptr(eu), N.ptr(ei), N.ptr(ids[b0:b1]), b1 - b0, nu, ni, d,
+            N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+            float(mask_value), k, N.ptr(val[b0:b1]), N.ptr(idx[b0:b1]), N.ptr(ws), ws_bytes,
+            N.stream_handle(eu.device)), "lg_score_topk_batch_f32")
+    return val, idx
+
+
 def score_dense(eu: torch.Tensor, ei: torch.Tensor, excl: RowSets | None = None,
                 mask_value: float = MASK_VALUE) -> torch.Tensor:
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
@@ -1016,7 +1094,7 @@ class TileWeights:
 
 def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
                       drop: bool = True, eu: torch.Tensor | None = None,
-                      ei: torch.Tensor | None = None, users: slice | None = None,
+                      ei: torch.Tensor | None = None, users=None,
                       tile: int = 2048, items: slice | None = None,
                       stats: dict | None = None, count_paths: bool = False,
                       col_bounds: bool = True, **_):
@@ -1030,7 +1108,9 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     into its running top-k list in the same pass. With a G factor (SpreadLightGCN) the
     per-(user, 64-column chunk) score bounds of lg_score_chunk_bound (bf16 MFMA) screen the
     columns, so only those whose bound times F can beat the list's k-th value get the exact
-    fp32 score chain. ``users`` restricts the output to a row range; ``items`` restricts the
+    fp32 score chain. ``users`` restricts the output to a row range (slice) or to any user ids
+    (tensor / list, any order, duplicates allowed: the walk then runs on the taken user-side
+    rows, bitwise the all-users rows); ``items`` restricts the
     candidates to an item range (the lists of disjoint item ranges merge, with
     merge_topk_lists, into the full lists: the multi-GPU item shard). (The two-kernel form
     -- F written per tile, then a top-K merge -- is a test reference, tests/_ref_paths.py.)
@@ -1057,11 +1137,16 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     if k > PEEL_K:
         return _spread_topk_tiled_peeled(A, lam, k, excl, drop, eu, ei, users, tile, items,
                                          stats, count_paths, col_bounds)
-    u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
+    dev = A.k_item.device
+    # users: a row range (slice) or any user ids (tensor / list: rows in that order)
+    ids = None if users is None or isinstance(users, slice) else _user_ids(users, A.n_users, dev)
+    if ids is not None:
+        u0, u1 = 0, int(ids.numel())
+    else:
+        u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
     i0, i1 = (0, A.n_items) if items is None else (max(0, items.start),
                                                    min(A.n_items, items.stop))
     n = u1 - u0
-    dev = A.k_item.device
     vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
     if n == 0 or i1 <= i0:
@@ -1070,11 +1155,21 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     tw = TileWeights(A, lam, tile)
     if i0:
         tw.seek(i0)
-    ex = excl.slice_rows(u0, u1) if excl is not None else None
-    eu_r = None if eu is None else eu[u0:u1]
+    rows = src = None
+    if ids is not None:
+        # the user side from the taken rows; the item side (the tiles) from the full A
+        if stats is not None and count_paths:
+            raise ValueError("count_paths takes a user range, not user ids")
+        rows, src = A.by_user.take(ids, return_index=True)
+        ex = excl.take(ids) if excl is not None else None
+        eu_r = None if eu is None else eu[ids]
+    else:
+        ex = excl.slice_rows(u0, u1) if excl is not None else None
+        eu_r = None if eu is None else eu[u0:u1]
     if stats is not None and count_paths:
         _count_rows(tw, A, u0, u1)
-    walk = TileWalk(A, u0, u1, i0, k, ex if drop else None, eu_r, ei, tile, col_bounds)
+    walk = TileWalk(A, u0, u1, i0, k, ex if drop else None, eu_r, ei, tile, col_bounds,
+                    rows=rows, edge_src=src)
     evs = [] if stats is not None else None
     for j0 in range(i0, i1, tile):
         if evs is not None:  # per-tile HIP events on the launch stream: build / bounds / walk
@@ -1100,7 +1195,8 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
         stats["walk_launches"] = stats.get("walk_launches", 0) + len(evs)
         stats["walk_ms_list"] = stats.get("walk_ms_list", []) + [e[2].elapsed_time(e[3]) for e in evs]
         stats["user_items"] = stats.get("user_items", 0) + len(evs) * int(
-            A.by_user.rowptr[u1] - A.by_user.rowptr[u0])
+            rows.col.numel() if rows is not None
+            else A.by_user.rowptr[u1] - A.by_user.rowptr[u0])
         stats["users"] = n
         stats["qstride"] = 0 if walk.d == 0 or walk.qbuf is None else walk.qbuf.shape[1]
         stats["nch"] = -(-tile // 64) if walk.d else 0
@@ -1120,9 +1216,13 @@ def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets
                               col_bounds: bool):
     """spread_topk_tiled for PEEL_K < k <= 1024 (see there): passes of <= PEEL_K entries, each
     excluding what the earlier ones found."""
-    u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
-    n = u1 - u0
     dev = A.k_item.device
+    ids = None if users is None or isinstance(users, slice) else _user_ids(users, A.n_users, dev)
+    if ids is not None:
+        users, u0, u1 = ids, 0, int(ids.numel())
+    else:
+        u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
+    n = u1 - u0
     vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
     ex = excl if drop else None
@@ -1140,7 +1240,8 @@ def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets
             e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             e[0].record()
         hit = (i >= 0).nonzero(as_tuple=True)
-        found = RowSets.from_pairs(hit[0] + u0, i[hit], n_rows, A.n_items, dev)
+        found = RowSets.from_pairs(hit[0] + u0 if ids is None else ids[hit[0]], i[hit], n_rows,
+                                   A.n_items, dev)
         ex = found if ex is None else RowSets.union(ex, found)
         if stats is not None:
             e[1].record()
@@ -1227,12 +1328,22 @@ class TileWalk:
 
     def __init__(self, A: Interactions, u0: int, u1: int, i0: int, k: int,
                  ex: RowSets | None, eu=None, ei=None, tile: int = 2048,
-                 col_bounds: bool = True):
+                 col_bounds: bool = True, rows: RowSets | None = None, edge_src=None):
         self.A, self.u0, self.u1, self.i0, self.k, self.ex = A, u0, u1, i0, int(k), ex
         # the walk keeps its stream positions in 32 bits
         if A.by_user.col.numel() >= 2**31 or (ex is not None and ex.col.numel() >= 2**31):
             raise ValueError("the tile walk needs fewer than 2^31 interactions / exclusions")
         self.n = u1 - u0
+        # the user side of the walk: rows [u0, u1) of A, or ``rows`` -- any rows of A.by_user
+        # (RowSets.take(ids, return_index=True): edge_src = their positions in A.by_user.col,
+        # which the per-interaction factors of HybridScale are gathered by); ex, eu are then
+        # the taken rows too and u0 = 0, u1 = the number of rows
+        self.rows, self.edge_src = rows, edge_src
+        self._ra = (None, None)
+        if rows is not None:
+            if edge_src is None or (u0, u1) != (0, rows.n_rows):
+                raise ValueError("TileWalk(rows=): edge_src and u0, u1 = 0, rows.n_rows")
+            self.n = rows.n_rows
         self.dev = A.k_item.device
         self.vals = torch.full((self.n, self.k), float("-inf"), dtype=torch.float64,
                                device=self.dev)
@@ -1285,14 +1396,21 @@ class TileWalk:
             bnd = self.bounds(j0, width, scale)
         gb, q = bnd if bnd is not None else (None, None)
         nch = gb.shape[1] if gb is not None else 0
+        if self.rows is None:
+            u_rowptr, u_col, ra_edge = A.by_user.rowptr[self.u0:], A.by_user.col, scale.ra_edge
+        else:
+            if self._ra[0] is not scale:  # (one gather per lambda, not per tile)
+                self._ra = (scale, torch.cat([scale.ra_edge[self.edge_src],
+                                              scale.ra_edge.new_zeros(1)]))
+            u_rowptr, u_col, ra_edge = self.rows.rowptr, self.rows.col, self._ra[1]
         N.check(N.lib().lg_spread_tile_resource_topk_f64(
-            N.ptr(A.by_user.rowptr[self.u0:]), N.ptr(A.by_user.col), N.ptr(scale.ra_edge),
+            N.ptr(u_rowptr), N.ptr(u_col), N.ptr(ra_edge),
             self.n, N.ptr(lines), N.ptr(ovf), A.n_items, N.ptr(scale.rb), N.ptr(inv_cls), int(j0),
             int(tile), int(width), N.ptr(self.eu), N.ptr(self.ei), self.d, N.ptr(gb), nch,
             N.ptr(q), 0 if q is None else q.shape[1],
             N.ptr(ex.rowptr if ex is not None else None),
             N.ptr(ex.col if ex is not None else None), N.ptr(self.ex_cur), self.k,
-            int(bool(first)), N.ptr(self.vals), N.ptr(self.idxs), A.by_user.col.numel(),
+            int(bool(first)), N.ptr(self.vals), N.ptr(self.idxs), u_col.numel(),
             ex.col.numel() if ex is not None else 0, N.stream_handle(self.dev)),
             "lg_spread_tile_resource_topk_f64")
 
@@ -1395,17 +1513,54 @@ def dense_spread_fits(n_items: int, device, fraction: float = 0.25) -> bool:
 def spread_recommend(A: Interactions, lam: float, k: int, excl: RowSets | None,
                      drop: bool = True, eu: torch.Tensor | None = None,
                      ei: torch.Tensor | None = None, transpose: bool = False,
-                     tiled: bool | None = None):
+                     tiled: bool | None = None, users=None, tile: int | None = None):
     """Per-user top-k of (G *) A @ HybridS(A, general_W(^T), lam), dense (I x I matrices on
     the device) or factored over item tiles (tiled=None: dense when it fits). The two
     paths give the same values within a few ulp (the factored walk sums each column's paths
     in its own order) and the same lists except near-ties. general_W is exactly symmetric (entry (i, j) and (j, i) are
     the same sum, over the common users ascending, of the same fl(1/k_v)), so the
     reference's general_W.T overrides (model/SpreadMethod/recommend.py:89-91, :99-101)
-    are served by either path unchanged."""
+    are served by either path unchanged.
+
+    ``users`` (a tensor or list of user ids, any order, duplicates allowed) restricts the
+    result to those users: row j is bitwise row users[j] of the all-users call on the same
+    path. The user side (interaction rows, exclusion rows, eu rows) is taken for those ids;
+    the item side (W, or the general_W tiles) comes from the full A. ``tile`` is the tiled
+    path's tile width (default: spread_topk_tiled's)."""
     if tiled is None:
         tiled = not dense_spread_fits(A.n_items, A.k_item.device)
     if tiled:
-        return spread_topk_tiled(A, lam, k, excl, drop, eu, ei)
+        kw = {} if tile is None else {"tile": int(tile)}
+        return spread_topk_tiled(A, lam, k, excl, drop, eu, ei, users=users, **kw)
+    ids = None if users is None else _user_ids(users, A.n_users, A.k_item.device)
     W = spread_hybrid(A, lam)  # (= hybrid_weight(spread_general(A), ..., transpose))
+    if ids is not None:
+        return _spread_topk_users(A, W, ids, k, excl, drop, eu, ei)
     return spread_topk(A, W, k, excl, drop, eu, ei)
+
+
+def _spread_topk_users(A: Interactions, W: torch.Tensor, ids: torch.Tensor, k: int,
+                       excl: RowSets | None, drop: bool, eu, ei):
+    """spread_topk for the users ``ids`` only: lg_spread_resource_f64 on the taken
+    interaction rows (F rows of those users, block by block), then rows_topk with the taken
+    exclusion and eu rows."""
+    I = A.n_items
+    rows = A.by_user.take(ids)
+    ex = excl.take(ids) if excl is not None else None
+    eu_r = None if eu is None else eu[ids]
+    n = rows.n_rows
+    W = W.contiguous()
+    vals = torch.empty((n, k), dtype=torch.float64, device=W.device)
+    idxs = torch.empty((n, k), dtype=torch.int64, device=W.device)
+    block = max(1, min(n, (1 << 30) // max(1, I * 8)))  # ~1 GiB of F per block
+    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=W.device)
+    for b0 in range(0, n, block):
+        b1 = min(n, b0 + block)
+        Fb = buf[: b1 - b0]
+        N.check(N.lib().lg_spread_resource_f64(
+            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
+            Fb.stride(0), N.stream_handle(W.device)), "lg_spread_resource_f64")
+        v, i = rows_topk(Fb, k, ex.slice_rows(b0, b1) if ex is not None else None, drop,
+                         None if eu_r is None else eu_r[b0:b1], ei)
+        vals[b0:b1], idxs[b0:b1] = v, i
+    return vals, idxs

@@ -9,6 +9,10 @@ the tiles it cannot rule out), below it lg_score_topk_f32 itself; the lists are 
 for bit, ties ordered (score desc, item asc). RECOMMEND["k"] up to 128 takes those kernels;
 128 < k <= 1024 takes lg_score_topk_wide_f32 (the same scores and order, lists in global
 slabs); larger k raises.
+
+recommendForUsers is the request form: the same lists for a few user ids only, through
+ops.score_topk_users (lg_score_topk_batch_f32 for short lists: no rows gathered, no other
+user's scores computed).
 """
 import numpy as np
 import pandas as pd
@@ -60,6 +64,31 @@ def recommendForAllUser(model, user_num: int, item_num: int,
     save_recs(recs, cfg.RECOMMEND["save_path"] + "all_user_recommend_dict_" + cfg.MODEL["name"]
               + "_" + str(cfg.RECOMMEND["k"]) + ".npy")
     return recs
+
+
+def topk_for_users(model, user_ids, user_num: int, item_num: int, train_edge_index,
+                   val_edge_index, k: int):
+    """Device result of recommendForUsers: (scores [B,k] fp32, items [B,k] int64), row j =
+    topk_for_all_users' row user_ids[j] (ops.score_topk_users: no score row of any other
+    user is computed)."""
+    w_u = model.users_emb.weight.detach()
+    dev = gpu_device(w_u)
+    eu = w_u.to(dev, torch.float32).contiguous()
+    ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
+    excl = exclusion_from_coo(user_num, item_num, train_edge_index, val_edge_index, device=dev)
+    return ops.score_topk_users(eu, ei, user_ids, k, excl, mask_value=float(-(1 << 10)))
+
+
+def recommendForUsers(model, user_ids, user_num: int, item_num: int,
+                      train_edge_index: torch.Tensor, val_edge_index: torch.Tensor,
+                      test_edge_index: torch.Tensor, k: int) -> dict:
+    """{uid: top-k items} for the given user ids only: the matching entries of
+    recommendForAllUser (same -1024 mask, same lists). Writes no file. An id outside
+    [0, user_num) raises ValueError."""
+    ids = [int(u) for u in torch.as_tensor(user_ids).reshape(-1).tolist()]
+    _, idx = topk_for_users(model, ids, user_num, item_num, train_edge_index, val_edge_index, k)
+    rows = topk_to_dict(idx)
+    return {u: rows[j] for j, u in enumerate(ids)}
 
 
 def recommendLightGCN(user_num: int, item_num: int, rating_df: pd.DataFrame,

@@ -7,6 +7,7 @@ from const import cfg
 from lgcnhs.features import features_tensor
 from lgcnhs.recs import gpu_device, save_recs, topk_to_dict
 from model.LightGCN.recommend import buildGraph, topk_for_all_users  # noqa: F401
+from model.LightGCN.recommend import recommendForUsers, topk_for_users  # noqa: F401
 from utils.log import logger
 
 

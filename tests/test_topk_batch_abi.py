@@ -1,0 +1,116 @@
+"""K2b (top-K for a short list of users, csrc/topk_batch.hip), C ABI side:
+lg_score_topk_batch_ws_bytes and lg_score_topk_batch_f32 are exported by both libraries,
+refuse every bad call before any launch with the entry's name in lg_last_error(), and size
+the workspace by one partial list per (workgroup, user). CPU only (no kernel runs)."""
+import ctypes
+
+import pytest
+
+NAMES = ("lg_score_topk_batch_ws_bytes", "lg_score_topk_batch_f32")
+LG_OK, LG_ERR_ARG, LG_ERR_WORKSPACE = 0, 1, 3
+ME = b"lg_score_topk_batch_f32"
+
+z = ctypes.c_void_p(0)
+one = ctypes.c_void_p(16)  # never dereferenced: validation fails first
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from lgcnhs import _native as N
+    return N.load_library()
+
+
+def call(lib, eu=one, ei=one, ids=one, n_batch=8, n_table=1000, n_items=1000, dim=64, rp=z,
+         col=z, k=20, val=one, idx=one, ws=one, ws_bytes=1 << 40):
+    return lib.lg_score_topk_batch_f32(eu, ei, ids, n_batch, n_table, n_items, dim, rp, col,
+                                       -1024.0, k, val, idx, ws, ws_bytes, z)
+
+
+def refused(lib, **kw):
+    assert call(lib, **kw) == LG_ERR_ARG, kw
+    msg = lib.lg_last_error()
+    assert ME in msg, (kw, msg)
+    return msg
+
+
+def test_exported_by_both_libraries():
+    from lgcnhs import _native as N
+    prod, ref = N.load_library(), N.ref_lib()
+    assert N.ABI_VERSION == 17 == prod.lg_abi_version() == ref.lg_abi_version()
+    for name in NAMES:
+        assert name in N.SIGNATURES, name
+        assert hasattr(prod, name), name
+        assert hasattr(ref, name), name
+
+
+def test_null_pointers_are_refused(lib):
+    for name in ("eu", "ei", "val", "idx"):
+        assert b"null" in refused(lib, **{name: z})
+
+
+def test_bad_batch_k_and_dim_are_refused(lib):
+    for nb in (0, -1, 65, 1000):
+        assert b"n_batch" in refused(lib, n_batch=nb)
+    for k in (0, -1, 129, 1024):
+        assert b"k=" in refused(lib, k=k)
+    for dim in (0, 16, 48, 256):
+        assert b"dim" in refused(lib, dim=dim)
+    assert b"n_items" in refused(lib, n_items=0)
+    assert b"n_items" in refused(lib, n_items=2**31 - 1)
+    assert b"n_table_users" in refused(lib, n_table=0)
+
+
+def test_half_set_exclusion_pair_is_refused(lib):
+    assert b"ex_rowptr" in refused(lib, rp=one, col=z)
+    assert b"ex_rowptr" in refused(lib, rp=z, col=one)
+
+
+@pytest.mark.parametrize("nb,k", [(1, 1), (8, 20), (64, 128)])
+def test_short_workspace(lib, nb, k):
+    need = lib.lg_score_topk_batch_ws_bytes(nb, 1000, 64, k)
+    assert need > 0
+    for ws, nbytes in ((one, need - 1), (one, 0), (z, need), (z, 0)):
+        assert call(lib, n_batch=nb, k=k, ws=ws, ws_bytes=nbytes) == LG_ERR_WORKSPACE
+        msg = lib.lg_last_error()
+        assert ME in msg and b"workspace" in msg
+
+
+def test_ws_bytes_shape(lib):
+    """One partial list of k 8-byte entries per (workgroup, user): at most 512 workgroups and
+    never more than 16-item tiles; monotone in n_batch and k; 0 for arguments the call
+    refuses."""
+    f = lib.lg_score_topk_batch_ws_bytes
+    I = 1_000_000
+    assert f(64, I, 64, 128) == 512 * 64 * 128 * 8
+    assert f(1, I, 32, 1) == 512 * 8
+    assert f(8, 40, 64, 20) == 3 * 8 * 20 * 8  # 3 tiles
+    assert f(8, 1, 128, 20) == 8 * 20 * 8
+    prev = 0
+    for nb in range(1, 65):
+        cur = f(nb, I, 64, 20)
+        assert cur > prev
+        prev = cur
+    prev = 0
+    for k in range(1, 129):
+        cur = f(16, I, 64, k)
+        assert cur > prev
+        prev = cur
+    for bad in ((0, I, 64, 20), (65, I, 64, 20), (8, 0, 64, 20), (8, 2**31 - 1, 64, 20),
+                (8, I, 48, 20), (8, I, 64, 0), (8, I, 64, 129)):
+        assert f(*bad) == 0, bad
+
+
+def test_user_ids_are_validated_on_the_host():
+    """ops.score_topk_users / RowSets-free id check: a list or CPU tensor with an id outside
+    the table raises ValueError before anything touches the device."""
+    import torch
+    from lgcnhs import ops
+    with pytest.raises(ValueError, match="user id"):
+        ops._user_ids([0, 5, 10], 10, "cpu")
+    with pytest.raises(ValueError, match="user id"):
+        ops._user_ids(torch.tensor([-1, 2]), 10, "cpu")
+    with pytest.raises(ValueError, match="integers"):
+        ops._user_ids([0.5, 1.0], 10, "cpu")
+    t = ops._user_ids([3, 1, 3], 10, "cpu")
+    assert t.dtype == torch.int64 and t.tolist() == [3, 1, 3]
+    assert ops._user_ids([], 10, "cpu").numel() == 0
