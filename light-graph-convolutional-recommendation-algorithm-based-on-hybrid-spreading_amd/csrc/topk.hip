@@ -19,58 +19,15 @@
 // binary-searched only for list entries, in batch when the list is compacted: an excluded
 // item takes mask_value (-1024) before the sort, which is exactly the reference's masked
 // top-k. Lists are compacted by the wave-wide bitonic sort of common.h. Order: (score
-// desc, item asc). The main loop thus issues no global load but the item tiles.
+// desc, item asc). The main loop thus issues no global load but the item tiles. The loads,
+// the filter, the threshold rule and the lazy exclusion are in score_stream.h, shared with K2w
+// (topk_wide.hip) and K2b (topk_batch.hip).
 #include <stdlib.h>
 
 #include "common.h"
+#include "score_stream.h"
 
 namespace lg {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int Q>
-__device__ __forceinline__ void load_piece(const float *__restrict__ p, float (&v)[Q]) {
-  const float4 *p4 = reinterpret_cast<const float4 *>(p);
-#pragma unroll
-  for (int t = 0; t < Q / 4; ++t) {
-    const float4 q = p4[t];
-    v[4 * t + 0] = q.x;
-    v[4 * t + 1] = q.y;
-    v[4 * t + 2] = q.z;
-    v[4 * t + 3] = q.w;
-  }
-}
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// Item-tile loads: raw buffer loads through a per-tile descriptor whose base is the tile's
-// first row and whose record count is the bytes left in the table (0 past its end), so rows
-// beyond n_items read as 0 and every tile issues the same LT loads with no branch and no
-// per-lane address arithmetic. Compiler-visible (__builtin_amdgcn_raw_buffer_load_b128):
-// hipcc counts these loads itself and places each s_waitcnt vmcnt before the first use.
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-template <int D>
-__device__ __forceinline__ void load_item_tile(const float *ei, int64_t n_items, int64_t it,
-                                               int voff, f32x4v (&v)[D / 16]) {
-  constexpr int TB = 16 * D * 4;  // bytes of one 16-item tile
-  const int rem = (int)(n_items - it);  // items left in the table (n_items < 2^31)
-  const int num = rem >= 16 ? TB : (rem > 0 ? rem * (D * 4) : 0);
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc((void *)(ei + it * D), 0, num, 0x00020000);
-#pragma unroll
-  for (int t = 0; t < D / 16; ++t)
-    v[t] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16 * t, 0, 0));
-}
-
-// max of the four scores of an MFMA result: two v_maximum3_f32 (gfx950), compiler-visible, so
-// hipcc pads the MFMA-result wait states itself. NaN-propagating: callers test
-// !(max4(a) <= thr), which sends a NaN score to the exact per-element test (sc > thr) instead
-// of hiding the tile's other scores behind it.
-__device__ __forceinline__ float max4(f32x4 a) {
-  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a[0], a[1]),
-                                       __builtin_elementwise_maximum(a[2], a[3]));
-}
-__device__ __forceinline__ bool above(float m, float thr) { return !(m <= thr); }
 
 // One wave: NG groups of 16 users; the block's waves work independently.
 //
@@ -114,7 +71,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk(
   bool uvalid[NG];
   int64_t ex_pos[NG], ex_hi[NG];
   int cnt[NG], chk[NG];
-  float tau[NG], thr[NG];
+  float thr[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int64_t u = ubase + g * 16 + ul;
@@ -129,20 +86,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk(
     }
     cnt[g] = 0;
     chk[g] = 0;
-    tau[g] = neg_inf<float>();
     thr[g] = (uvalid[g] && probe != 1) ? neg_inf<float>() : __builtin_huge_valf();
     // probe == 1 (measurement builds only, see topk_probe()): no candidate ever enters
   }
   const uint64_t same_user = 0x0001000100010001ull << ul;
 
-  // Exclusion is applied lazily: a candidate enters on its raw score (or on the mask value
-  // when that alone beats tau), and the entries [chk, n) added since the user's last
-  // compaction are checked when the list is compacted. Their items all lie in
-  // [previous limit, lim), and ex_pos is the user's first excluded item not yet passed
-  // (>= the previous limit, or the row start: items below i0 are harmless), so the
-  // excluded items to test are one ascending run ex_col[ex_pos ..) read 64 at a time,
-  // coalesced, and binary-searched in LDS. Exact: an excluded item would enter with
-  // mask_value, and mask_value > tau admits every item.
+  // Compact user u of group g, all of whose items so far are below lim: the entries [chk, n)
+  // added since its last compaction get the lazy exclusion (mask_excluded_run; ex_pos starts
+  // at the row start), then the best k stay, sorted.
   auto compact_user = [&](int g, int u, int lim) __attribute__((always_inline)) {
     const int n = __shfl(cnt[g], u);
     const int c0 = __shfl(chk[g], u);
@@ -150,44 +101,22 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk(
     const int64_t hi = __shfl(ex_hi[g], u);
     float *ks = &cs[wave][g][u][0];
     int *is = &ci[wave][g][u][0];
-    if (n > c0) {
-      while (pos < hi) {
-        const int64_t e = pos + lane;
-        const int32_t x = e < hi ? ex_col[e] : 0x7fffffff;
-        const int nin = __popcll(__ballot(x < lim));  // ascending: a prefix of the lanes
-        if (nin == 0) break;
-        exs[wave][lane] = x;
-        wave_sync();
-        for (int j = c0 + lane; j < n; j += 64) {
-          const int item = is[j];
-          int a = 0, b = nin;  // first index with exs[] >= item
-          while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (exs[wave][mid] < item) a = mid + 1;
-            else b = mid;
-          }
-          if (a < nin && exs[wave][a] == item) ks[j] = mask_value;
-        }
-        wave_sync();
-        pos += nin;
-        if (nin < 64) break;
-      }
-    }
+    pos = mask_excluded_run(
+        ex_col, pos, hi, lim, exs, wave, c0, n, [&](int j) { return is[j]; },
+        [&](int j) { ks[j] = mask_value; });
     float t;
     int tid;
     const int nc = wave_compact<float, M>(ks, is, n, k, t, tid);
     if (ul == u) {
       cnt[g] = nc;
       chk[g] = nc;
-      tau[g] = t;
       ex_pos[g] = pos;
-      // a masked (excluded) item would enter with mask_value: admit everything then
-      thr[g] = !uvalid[g] ? __builtin_huge_valf() : (mask_value > t ? neg_inf<float>() : t);
+      thr[g] = entry_thr(uvalid[g], mask_value, t);
     }
   };
 
   // acc[g][r] = score(user ubase + 16g + ul, item i0 + 16t + 4gq + r)
-  auto mfma_tile = [&](const f32x4v(&af)[LT], f32x4 (&acc)[NG]) __attribute__((always_inline)) {
+  auto mfma_tile = [&](const f32x4(&af)[LT], f32x4 (&acc)[NG]) __attribute__((always_inline)) {
 #pragma unroll
     for (int g = 0; g < NG; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     // s outer / g inner: NG independent accumulation chains interleave on the MFMA pipe
@@ -261,7 +190,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk(
   // merges their pending state into the loop header and waits for them inside the loop
   __builtin_amdgcn_s_waitcnt(0x0F70);
   if (n_t > 0) {
-    f32x4v afA[LT], afB[LT];
+    f32x4 afA[LT], afB[LT];
     f32x4 accA[NG], accB[NG];
     load_item_tile<D>(ei, n_items, i0, voff, afA);
     load_item_tile<D>(ei, n_items, i0 + 16, voff, afB);
@@ -709,7 +638,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_topk_ring(
         item[j] = (int)i0 + (tix << 4) + (int)(kbits[j] & kRowMask);
       }
     }
-    // the lazy exclusion of the entries [c0, n), in registers
+    // the lazy exclusion of the entries [c0, n), in registers (score_stream.h's
+    // mask_excluded_run is the LDS-list form of the same rule)
     if (n > c0) {
       while (pos < hi) {
         const int64_t e = pos + lane;
@@ -1604,12 +1534,6 @@ static size_t screened_part_bytes(int64_t n_users, int k, int ns) {
 }
 static size_t screened_slab_bytes(int64_t n_users, int k, int ns) {
   return (size_t)ns * (size_t)n_users * 64 * (size_t)screen_slab_m(k) * sizeof(uint2);
-}
-
-static int64_t split_len(int64_t n_items, int n_splits) {
-  int64_t per = (n_items + n_splits - 1) / n_splits;
-  per = (per + 15) / 16 * 16;
-  return per < 16 ? 16 : per;
 }
 
 // the screened kernel's splits: at least one per 2^20 items (k_topk_ring's 16-bit tile

@@ -15,7 +15,8 @@
 // divided over every wave of a grid that fills the device: wave w of the grid scores the items
 // [w ipw, (w + 1) ipw). A wave keeps one candidate list per user in LDS (CAP = 64 M entries,
 // M = 1 / 2 / 4 for k <= 32 / 64 / 128), exclusion applied lazily at compaction exactly as in
-// k_score_topk (the exclusion CSR is the full table's, indexed by the user id). At the end the
+// k_score_topk (the exclusion CSR is the full table's, indexed by the user id; the routine, the
+// loads, the filter and the threshold rule are the one text of score_stream.h). At the end the
 // waves of a workgroup merge their lists pairwise in LDS (a tree: log2(WAVES) steps), so the
 // workspace holds one sorted partial list per (workgroup, user); k_topk_batch_merge then
 // merges a user's R partial lists with 16 waves, each taking every 16th list, and the same
@@ -25,52 +26,14 @@
 // LDS per workgroup: WAVES NG M x 8 KiB of lists; WAVES = min(4, 16 / (NG M)) keeps that within
 // 128 KiB (one workgroup per CU at NG M = 16, two where the lists take <= 64 KiB).
 #include "common.h"
+#include "score_stream.h"
 
 namespace lg {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kBatchMax = 64;     // users per call
 constexpr int kMaxBlocks = 512;   // workgroups of the scoring grid: partial lists per user
 constexpr int kMergeWaves = 16;   // waves of k_topk_batch_merge's workgroup (one per user)
-
-template <int Q>
-__device__ __forceinline__ void load_piece(const float *__restrict__ p, float (&v)[Q]) {
-  const float4 *p4 = reinterpret_cast<const float4 *>(p);
-#pragma unroll
-  for (int t = 0; t < Q / 4; ++t) {
-    const float4 q = p4[t];
-    v[4 * t + 0] = q.x;
-    v[4 * t + 1] = q.y;
-    v[4 * t + 2] = q.z;
-    v[4 * t + 3] = q.w;
-  }
-}
-
-// Item-tile loads as in k_score_topk: raw buffer loads through a per-tile descriptor whose
-// record count is the bytes left below `end` (0 past it), so rows beyond the wave's range read
-// as 0 without touching memory, and every tile issues the same D / 16 loads with no branch.
-template <int D>
-__device__ __forceinline__ void load_item_tile(const float *ei, int64_t end, int64_t it,
-                                               int voff, f32x4 (&v)[D / 16]) {
-  constexpr int TB = 16 * D * 4;  // bytes of one 16-item tile
-  const int64_t rem64 = end - it;
-  const int rem = rem64 > 16 ? 16 : (int)rem64;
-  const int num = rem >= 16 ? TB : (rem > 0 ? rem * (D * 4) : 0);
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)(ei + (rem > 0 ? it : 0) * D), 0, num, 0x00020000);
-#pragma unroll
-  for (int t = 0; t < D / 16; ++t)
-    v[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16 * t, 0, 0));
-}
-
-// NaN-propagating max of an MFMA result's four scores (callers test !(max4(a) <= thr))
-__device__ __forceinline__ float max4(f32x4 a) {
-  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a[0], a[1]),
-                                       __builtin_elementwise_maximum(a[2], a[3]));
-}
-__device__ __forceinline__ bool above(float m, float thr) { return !(m <= thr); }
 
 // One wave: all the request's users (NG groups of 16; slot b = 16 g + (lane & 15) is row b of
 // the request), the items [w ipw, (w + 1) ipw) of the catalog, w = the wave's index in the grid.
@@ -109,7 +72,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_batch(
   bool uvalid[NG];
   int64_t ex_pos[NG], ex_hi[NG];
   int cnt[NG], chk[NG];
-  float tau[NG], thr[NG];
+  float thr[NG];
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int b = g * 16 + ul;
@@ -131,17 +94,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_batch(
     }
     cnt[g] = 0;
     chk[g] = 0;
-    tau[g] = neg_inf<float>();
     thr[g] = uvalid[g] ? neg_inf<float>() : __builtin_huge_valf();
   }
   const uint64_t same_user = 0x0001000100010001ull << ul;
 
-  // Lazy exclusion, as in k_score_topk: a candidate enters on its raw score, and the entries
-  // [chk, n) added since the user's last compaction are checked when the list is compacted.
-  // Their items lie in [previous limit, lim) and ex_pos is the user's first excluded item not
-  // yet passed, so the excluded items to test are one ascending run ex_col[ex_pos ..) read 64
-  // at a time and binary-searched in LDS. Exact: an excluded item would enter with mask_value,
-  // and mask_value > tau admits every item.
+  // Compact user u of group g, all of whose items so far are below lim: the entries [chk, n)
+  // added since its last compaction get the lazy exclusion (mask_excluded_run; ex_pos starts
+  // at the user's first excluded item inside the wave's range), then the best k stay, sorted.
   auto compact_user = [&](int g, int u, int lim) __attribute__((always_inline)) {
     const int n = __shfl(cnt[g], u);
     const int c0 = __shfl(chk[g], u);
@@ -149,39 +108,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_batch(
     const int64_t hi = __shfl(ex_hi[g], u);
     float *ks = &cs[wave][g * 16 + u][0];
     int *is = &ci[wave][g * 16 + u][0];
-    if (n > c0) {
-      while (pos < hi) {
-        const int64_t e = pos + lane;
-        const int32_t x = e < hi ? ex_col[e] : 0x7fffffff;
-        const int nin = __popcll(__ballot(x < lim));  // ascending: a prefix of the lanes
-        if (nin == 0) break;
-        exs[wave][lane] = x;
-        wave_sync();
-        for (int j = c0 + lane; j < n; j += 64) {
-          const int item = is[j];
-          int a = 0, b = nin;  // first index with exs[] >= item
-          while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (exs[wave][mid] < item) a = mid + 1;
-            else b = mid;
-          }
-          if (a < nin && exs[wave][a] == item) ks[j] = mask_value;
-        }
-        wave_sync();
-        pos += nin;
-        if (nin < 64) break;
-      }
-    }
+    pos = mask_excluded_run(
+        ex_col, pos, hi, lim, exs, wave, c0, n, [&](int j) { return is[j]; },
+        [&](int j) { ks[j] = mask_value; });
     float t;
     int tid;
     const int nc = wave_compact<float, M>(ks, is, n, k, t, tid);
     if (ul == u) {
       cnt[g] = nc;
       chk[g] = nc;
-      tau[g] = t;
       ex_pos[g] = pos;
-      // a masked (excluded) item would enter with mask_value: admit everything then
-      thr[g] = !uvalid[g] ? __builtin_huge_valf() : (mask_value > t ? neg_inf<float>() : t);
+      thr[g] = entry_thr(uvalid[g], mask_value, t);
     }
   };
 
@@ -259,24 +196,24 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_batch(
   if (n_t > 0) {
     f32x4 afA[LT], afB[LT];
     f32x4 accA[NG], accB[NG];
-    load_item_tile<D>(ei, i1, i0, voff, afA);
-    load_item_tile<D>(ei, i1, i0 + 16, voff, afB);
+    load_item_tile<D, true>(ei, i1, i0, voff, afA);
+    load_item_tile<D, true>(ei, i1, i0 + 16, voff, afB);
     mfma_tile(afA, accA);
-    load_item_tile<D>(ei, i1, i0 + 32, voff, afA);
+    load_item_tile<D, true>(ei, i1, i0 + 32, voff, afA);
     // invariant at step t: acc[t%2] = tile t; buffer (t+1)%2 = tile t+1 (landed or in
     // flight); buffer t%2 = tile t+2 in flight
     for (int t = 0;; t += 2) {
       // ---- even step: tile t in accA, tile t+1 in afB
       mfma_tile(afB, accB);
       bool hit = any_cand(accA);
-      load_item_tile<D>(ei, i1, i0 + (int64_t)(t + 3) * 16, voff, afB);
+      load_item_tile<D, true>(ei, i1, i0 + (int64_t)(t + 3) * 16, voff, afB);
       if (hit) insert_tile(t, accA);
       maybe_compact(step_lim(t));
       if (t + 1 >= n_t) break;
       // ---- odd step: tile t+1 in accB, tile t+2 in afA
       mfma_tile(afA, accA);
       hit = any_cand(accB);
-      load_item_tile<D>(ei, i1, i0 + (int64_t)(t + 4) * 16, voff, afA);
+      load_item_tile<D, true>(ei, i1, i0 + (int64_t)(t + 4) * 16, voff, afA);
       if (hit) insert_tile(t + 1, accB);
       maybe_compact(step_lim(t + 1));
       if (t + 2 >= n_t) break;

@@ -8,8 +8,9 @@
 //     _, recommendations = torch.topk(score, k)
 //
 // The score, the software pipeline, the one-max-one-compare filter and the admission rule are
-// k_score_topk's (see the head of topk.hip): 16 users per wave as MFMA B fragments, 16-item
-// tiles as A fragments through raw buffer loads, the v_mfma_f32_16x16x4_f32 chain
+// k_score_topk's (see the head of topk.hip; the loads, the filter, the threshold rule and the
+// lazy exclusion are the one text of score_stream.h): 16 users per wave as MFMA B fragments,
+// 16-item tiles as A fragments through raw buffer loads, the v_mfma_f32_16x16x4_f32 chain
 //     acc = 0; for s < Q: for g < 4: acc = fmaf(u[g*Q+s], i[g*Q+s], acc),
 // and a score enters a user's list on sc > thr, thr = the running k-th value (-inf while
 // mask_value would itself enter, +inf for padding users). NaN and -inf never rank.
@@ -33,49 +34,10 @@
 // Several splits: every (split, user) slab ends with its best k entries sorted (padded with
 // {-inf, -1}), and k_topk_wide_merge reads the slabs' first k entries.
 #include "common.h"
+#include "score_stream.h"
 
 namespace lg {
 namespace wide {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int Q>
-__device__ __forceinline__ void load_piece(const float *__restrict__ p, float (&v)[Q]) {
-  const float4 *p4 = reinterpret_cast<const float4 *>(p);
-#pragma unroll
-  for (int t = 0; t < Q / 4; ++t) {
-    const float4 q = p4[t];
-    v[4 * t + 0] = q.x;
-    v[4 * t + 1] = q.y;
-    v[4 * t + 2] = q.z;
-    v[4 * t + 3] = q.w;
-  }
-}
-
-// Item-tile loads (k_score_topk's): raw buffer loads through a per-tile descriptor whose base
-// is the tile's first row and whose record count is the bytes left in the table (0 past its
-// end), so rows beyond n_items read as 0 with no branch. Compiler-visible: hipcc places each
-// s_waitcnt vmcnt before the first use.
-template <int D>
-__device__ __forceinline__ void load_item_tile(const float *ei, int64_t n_items, int64_t it,
-                                               int voff, f32x4 (&v)[D / 16]) {
-  constexpr int TB = 16 * D * 4;  // bytes of one 16-item tile
-  const int rem = (int)(n_items - it);  // items left in the table (n_items < 2^31)
-  const int num = rem >= 16 ? TB : (rem > 0 ? rem * (D * 4) : 0);
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc((void *)(ei + it * D), 0, num, 0x00020000);
-#pragma unroll
-  for (int t = 0; t < D / 16; ++t)
-    v[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16 * t, 0, 0));
-}
-
-// NaN-propagating max of an MFMA result's four scores; callers test !(max4(a) <= thr), which
-// sends a NaN score to the exact per-element test (sc > thr).
-__device__ __forceinline__ float max4(f32x4 a) {
-  return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a[0], a[1]),
-                                       __builtin_elementwise_maximum(a[2], a[3]));
-}
-__device__ __forceinline__ bool above(float m, float thr) { return !(m <= thr); }
 
 // A list entry: x = the score's bits, y = the item (kPadId / -1 for padding).
 __device__ __forceinline__ uint2 make_entry(float v, int id) {
@@ -197,12 +159,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_wide(
 #endif
 
   // Compact user u (0..15) of this wave, all of whose items so far are below lim. Entries
-  // [chk, n) were added since the last compaction on their raw scores: their items lie in
-  // [previous lim, lim), and ex_pos is the user's first excluded item not yet passed, so the
-  // excluded items to test are one ascending run ex_col[ex_pos ..) read 64 at a time. Exact:
-  // an excluded item would enter with mask_value, and mask_value > tau admits every item.
-  // Leaves the best min(n, k) entries sorted in ws[0 ..) and returns their number; unless
-  // `fin`, writes them back to the slab.
+  // [chk, n) were added since the last compaction on their raw scores and get the lazy
+  // exclusion (mask_excluded_run; ex_pos starts at the row start). Leaves the best min(n, k)
+  // entries sorted in ws[0 ..) and returns their number; unless `fin`, writes them back to the
+  // slab.
   auto compact_user = [&](int u, int lim, bool fin) __attribute__((always_inline)) {
     const int n = __shfl(cnt, u);
     const int c0 = __shfl(chk, u);
@@ -216,29 +176,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_wide(
     for (int e = lane; e < P; e += 64)
       ws[e] = e < n ? slab_load(slab + e) : make_entry(neg_inf<float>(), kPadId);
     wave_sync();
-    if (n > c0) {
-      while (pos < hi) {
-        const int64_t e = pos + lane;
-        const int32_t x = e < hi ? ex_col[e] : 0x7fffffff;
-        const int nin = __popcll(__ballot(x < lim));  // ascending: a prefix of the lanes
-        if (nin == 0) break;
-        exs[wave][lane] = x;
-        wave_sync();
-        for (int j = c0 + lane; j < n; j += 64) {
-          const int item = (int)ws[j].y;
-          int a = 0, b = nin;  // first index with exs[] >= item
-          while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (exs[wave][mid] < item) a = mid + 1;
-            else b = mid;
-          }
-          if (a < nin && exs[wave][a] == item) ws[j].x = __builtin_bit_cast(uint32_t, mask_value);
-        }
-        wave_sync();
-        pos += nin;
-        if (nin < 64) break;
-      }
-    }
+    pos = mask_excluded_run(
+        ex_col, pos, hi, lim, exs, wave, c0, n, [&](int j) { return (int)ws[j].y; },
+        [&](int j) { ws[j].x = __builtin_bit_cast(uint32_t, mask_value); });
     lds_bitonic_sort<(M >= 32 ? 4 : 1)>(ws, P);
     const int nc = n < k ? n : k;
     const float t = nc == k ? entry_val(ws[k - 1]) : neg_inf<float>();
@@ -249,8 +189,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_topk_wide(
       cnt = nc;
       chk = nc;
       ex_pos = pos;
-      // a masked (excluded) item would enter with mask_value: admit everything then
-      thr = !uvalid ? __builtin_huge_valf() : (mask_value > t ? neg_inf<float>() : t);
+      thr = entry_thr(uvalid, mask_value, t);
     }
     return nc;
   };
@@ -409,13 +348,6 @@ constexpr int kWideWaves = 4;  // 64 users per block
 
 static int wide_m(int k) { return k <= 256 ? 8 : (k <= 512 ? 16 : 32); }
 
-// (k_score_topk's split arithmetic)
-static int64_t split_len(int64_t n_items, int n_splits) {
-  int64_t per = (n_items + n_splits - 1) / n_splits;
-  per = (per + 15) / 16 * 16;
-  return per < 16 ? 16 : per;
-}
-
 static size_t wide_slab_bytes(int64_t n_users, int k, int ns) {
   return (size_t)ns * (size_t)n_users * 64 * (size_t)wide_m(k) * sizeof(uint2);
 }
@@ -460,7 +392,7 @@ extern "C" size_t lg_score_topk_wide_ws_bytes(int64_t n_users, int64_t n_items, 
   if (n_users <= 0 || n_items <= 0 || n_items >= 0x7fffffff || k < 1 || k > 1024 ||
       n_splits < 1 || n_splits > 4096)
     return 0;
-  const int64_t per = wide::split_len(n_items, n_splits);
+  const int64_t per = split_len(n_items, n_splits);
   const int ns = (int)((n_items + per - 1) / per);
   return wide_slab_bytes(n_users, k, ns);
 }
@@ -481,7 +413,7 @@ extern "C" int lg_score_topk_wide_f32(const float *eu, const float *ei, int64_t 
   LG_REQUIRE(!ex_rowptr == !ex_col, "lg_score_topk_wide_f32: ex_rowptr/ex_col must both be set");
   LG_REQUIRE(((uintptr_t)ws & 7) == 0, "lg_score_topk_wide_f32: workspace not 8-byte aligned");
   if (n_users == 0) return LG_OK;
-  const int64_t per = wide::split_len(n_items, n_splits);
+  const int64_t per = split_len(n_items, n_splits);
   const int ns = (int)((n_items + per - 1) / per);
   const size_t need = wide_slab_bytes(n_users, k, ns);
   if (!ws || ws_bytes < need) {
