@@ -278,6 +278,36 @@ int lg_score_topk_batch_f32(const float *eu, const float *ei, const int64_t *use
                             int32_t k, float *out_val, int64_t *out_idx, void *ws,
                             size_t ws_bytes, lg_stream_t stream);
 
+/* lg_score_topk_batch_f32 restricted to a candidate item set (csrc/topk_items.hip K2i): the
+ * request form of model/LightGCN/recommend.py:83-114 with a catalog filter. item_ids (device,
+ * int32) holds n_cand strictly ascending ids in [0, n_items). Row b of the outputs is the
+ * first k of {(v(user_ids[b], i), i) : i in item_ids} under (value desc, item id asc), v the
+ * fp32 chain score of lg_score_topk_f32 or mask_value where i is in the user's exclusion row;
+ * NaN and -inf never rank; shorter rows are padded with {-inf, -1}; the ids returned are real
+ * item ids. That is lg_score_topk_f32(eu, ei[item_ids], ...) with the exclusion columns
+ * renumbered to positions in item_ids and the ids mapped back, bit for bit, and with
+ * item_ids = 0 .. n_items-1 lg_score_topk_f32's rows themselves -- without gathering a row:
+ * only the candidates' rows of ei are read. user_ids, ex_rowptr / ex_col (the FULL table's
+ * exclusion CSR, indexed by user id) and out-of-range user ids as in lg_score_topk_batch_f32.
+ * n_batch in [1, 16], k in [1, 128], dim in {32, 64, 128}, 1 <= n_cand <= n_items < 2^31 - 1.
+ * Memory-safe on any list: an id outside [0, n_items) reads row 0 and never enters a list; a
+ * list that is not ascending gives unspecified lists. The candidate positions are divided over
+ * every wave of a grid that fills the device; the workspace holds one partial list per
+ * (workgroup, user): lg_score_topk_batch_items_ws_bytes = min(512, ceil(n_cand / 16)) x
+ * n_batch x k x 8, device-independent (0 for arguments the call refuses). */
+size_t lg_score_topk_batch_items_ws_bytes(int64_t n_batch, int64_t n_cand, int32_t dim,
+                                          int32_t k);
+/* model/LightGCN/recommend.py:83-114 for the users of one request over a candidate item set
+ * (above). LG_ERR_ARG on a null pointer, n_batch outside [1, 16], bad dim, k, n_items or
+ * n_cand, a half-set exclusion pair; LG_ERR_WORKSPACE when ws is NULL or short; all before any
+ * launch. Never allocates, never syncs. */
+int lg_score_topk_batch_items_f32(const float *eu, const float *ei, const int64_t *user_ids,
+                                  int64_t n_batch, int64_t n_table_users, int64_t n_items,
+                                  const int32_t *item_ids, int64_t n_cand, int32_t dim,
+                                  const int64_t *ex_rowptr, const int32_t *ex_col,
+                                  float mask_value, int32_t k, float *out_val, int64_t *out_idx,
+                                  void *ws, size_t ws_bytes, lg_stream_t stream);
+
 /* Dense masked score matrix G[u][i] (same score definition and mask as above), written
  * with leading dimension ldg. Replaces getAllocateMat's matmul + masks
  * (model/SpreadLightGCN/model.py:74-104, model/SpreadLightGCNOpti/model.py:139-169). */

@@ -246,6 +246,24 @@ class RowSets:
         out = RowSets(rowptr, self.col[src], n, self.n_cols)
         return (out, src) if return_index else out
 
+    def restrict_cols(self, cand: torch.Tensor) -> "RowSets":
+        """The rows with only the columns in ``cand`` (a strictly ascending device tensor of
+        column ids), renumbered to positions in ``cand``: n_cols becomes len(cand). Rows keep
+        their order and stay sorted."""
+        dev = self.rowptr.device
+        c = cand.to(dev, torch.int64).reshape(-1)
+        col = self.col.to(torch.int64)
+        if c.numel() == 0:
+            keep = torch.zeros_like(col, dtype=torch.bool)
+            pos = col
+        else:
+            pos = torch.searchsorted(c, col)
+            keep = c[pos.clamp(max=c.numel() - 1)] == col
+        kept = torch.zeros(col.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(keep, 0, out=kept[1:])
+        return RowSets(kept[self.rowptr], pos[keep].to(torch.int32), self.n_rows,
+                       int(c.numel()))
+
 
 _ADJ_CACHE: dict = {}
 

@@ -449,7 +449,7 @@ def screen_margins(un: torch.Tensor, ue: torch.Tensor, inorm: torch.Tensor,
 
 def score_topk(eu: torch.Tensor, ei: torch.Tensor, k: int, excl: RowSets | None = None,
                mask_value: float = MASK_VALUE, n_splits: int | None = None,
-               screen: bool | None = None):
+               screen: bool | None = None, items=None):
     """Top-k items per user by the masked e0 score; returns (values fp32 [U,k],
     indices int64 [U,k]) sorted by (score desc, item asc). screen=True runs
     lg_score_topk_screened_f32: a bf16 MFMA bound decides which 16-item tiles get the exact
@@ -459,11 +459,24 @@ def score_topk(eu: torch.Tensor, ei: torch.Tensor, k: int, excl: RowSets | None 
     128 < k <= 1024 runs lg_score_topk_wide_f32 (same score, mask, order and padding; the
     lists live in workspace slabs). There is no screened wide kernel: screen=True raises.
     When the slabs would pass WIDE_WS_CAP_BYTES the users are processed in consecutive
-    blocks; the result does not depend on the blocking."""
+    blocks; the result does not depend on the blocking.
+
+    items: restrict every user's ranking to a candidate item set (item_candidates' forms). The
+    all-users job runs the same kernels on the gathered sub-table ei[cand] with the exclusion
+    columns renumbered (screened, plain and wide dispatch by the sub-table's shape) and maps
+    the ids back: real item ids, rows shorter than k padded with {-inf, -1}. The gather is
+    noise next to the scoring of every user; the request form that gathers nothing is
+    score_topk_users(items=...)."""
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
     nu, d = eu.shape
     ni = ei.shape[0]
     k = int(k)
+    if items is not None:
+        cand = item_candidates(items, ni, eu.device)
+        if cand.numel() == 0:
+            return _padding(nu, k, eu.device)
+        return _score_topk_gathered(eu, ei, cand, k, excl, mask_value, n_splits=n_splits,
+                                    screen=screen)
     if k > WIDE_K_MAX:
         raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
     if k >= WIDE_K_MIN:
@@ -607,14 +620,94 @@ def _user_ids(users, n_users: int, device) -> torch.Tensor:
     return t.contiguous()
 
 
+ITEMS_CALL_USERS = 16  # users per lg_score_topk_batch_items_f32 call (csrc/topk_items.hip)
+# score_topk_users(items=...) sends lists of up to this many users (k <= 128) to
+# lg_score_topk_batch_items_f32, in chunks of ITEMS_CALL_USERS, and longer ones to score_topk
+# on the gathered sub-table. Set from profiles/topk_items.json (scripts/topk_items_time.py):
+# the largest B at which the entry beats the gather route (ei[cand], the renumbered exclusion
+# rows, score_topk_users on the sub-table, the id map) by more than the larger of the two
+# spreads for every candidate share, k and d timed at 100K and 1M items: 0.12-0.73 of its time
+# at B <= 16 (all 96 cases); at B = 32 it loses 8 of 32 cases (k = 100), at B = 64 every
+# k = 100 case (1.6-2.9x).
+ITEMS_BATCH_MAX_USERS = 16
+
+
+def item_candidates(items, n_items: int, device) -> torch.Tensor:
+    """The candidate set of an items= argument as the kernel takes it: an int32 tensor on
+    `device` of strictly ascending ids in [0, n_items).
+
+    A list, a numpy array or a CPU tensor of ids is sorted and de-duplicated on the host
+    (ValueError on a non-integer id or one outside [0, n_items)). A bool mask of length n_items
+    (host or device) gives its true positions. A device integer tensor is taken as it is -- the
+    caller guarantees that it is strictly ascending, nothing is checked and nothing syncs (the
+    kernel reads no memory outside the tables on any list: an id outside [0, n_items) never
+    ranks, a list that is not ascending gives unspecified lists). Empty sets are allowed."""
+    n_items = int(n_items)
+    t = items if isinstance(items, torch.Tensor) else torch.as_tensor(np.asarray(items))
+    if t.dtype == torch.bool:
+        if t.dim() != 1 or t.numel() != n_items:
+            raise ValueError(f"item mask of shape {tuple(t.shape)}, expected ({n_items},)")
+        return torch.nonzero(t).reshape(-1).to(device, torch.int32)
+    if t.numel() and (t.is_floating_point() or t.is_complex()):
+        raise ValueError("item ids must be integers")
+    t = t.reshape(-1)
+    if t.is_cuda:
+        return t.to(device, torch.int32).contiguous()
+    t = torch.unique(t.to(torch.int64))  # (sorted)
+    if t.numel() and (int(t[0]) < 0 or int(t[-1]) >= n_items):
+        raise ValueError(f"item id outside [0, {n_items})")
+    return t.to(torch.int32).to(device)
+
+
+def items_topk_grid(n_batch: int, n_cand: int, k: int, device) -> tuple:
+    """(workgroups, waves per workgroup, candidate positions per wave) of
+    lg_score_topk_batch_items_f32's scoring launch (the host code of csrc/topk_items.hip,
+    restated): batch_topk_grid's arithmetic for one user group over n_cand positions."""
+    m = 1 if k <= 32 else (2 if k <= 64 else 4)
+    waves = 4
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    tiles = (n_cand + 15) // 16
+    blocks = min(512, cus * (2 if waves * m <= 8 else 1), -(-tiles // waves))
+    ppw = -(-tiles // (blocks * waves)) * 16
+    busy = -(-n_cand // ppw)  # waves with candidates
+    return -(-busy // waves), waves, ppw
+
+
+def _padding(n_rows: int, k: int, device):
+    if not 1 <= k <= WIDE_K_MAX:
+        raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
+    return (torch.full((n_rows, k), float("-inf"), dtype=torch.float32, device=device),
+            torch.full((n_rows, k), -1, dtype=torch.int64, device=device))
+
+
+def _score_topk_gathered(eu, ei, cand, k, excl, mask_value, **kw):
+    """score_topk on the sub-table ei[cand] (exclusion columns renumbered to positions in
+    cand), ids mapped back through cand, -1 kept."""
+    c64 = cand.to(torch.int64)
+    ex = excl.restrict_cols(cand) if excl is not None else None
+    if ex is not None and ex.col.numel() == 0:
+        ex = None  # (no excluded candidate at all: an empty tensor has no pointer to pass)
+    v, i = score_topk(eu, ei[c64], k, ex, mask_value, **kw)
+    return v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
+
+
 def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
-                     excl: RowSets | None = None, mask_value: float = MASK_VALUE):
+                     excl: RowSets | None = None, mask_value: float = MASK_VALUE,
+                     items=None):
     """Top-k items for the given users only: (values fp32 [B, k], indices int64 [B, k]), row j
     = score_topk's row users[j] of the full tables bit for bit. users: a list or tensor of ids
     into eu and excl (any order, duplicates allowed); a list or CPU tensor is checked on the
     host (ValueError on a bad id). Up to BATCH_MAX_USERS users (k <= 128) run
     lg_score_topk_batch_f32 in chunks of 64 -- no embedding or exclusion rows are gathered;
-    longer lists and 128 < k <= 1024 run score_topk on the gathered rows."""
+    longer lists and 128 < k <= 1024 run score_topk on the gathered rows.
+
+    items: restrict the ranking to a candidate item set (item_candidates' forms: ids, a bool
+    mask, or a strictly ascending device tensor). Row j is then the first k of the candidates
+    under (score desc, item id asc), real item ids, rows shorter than k padded with
+    {-inf, -1}: score_topk(..., items=items)'s row users[j] bit for bit. Up to
+    ITEMS_BATCH_MAX_USERS users (k <= 128) run lg_score_topk_batch_items_f32 in chunks of 16
+    -- no item row is gathered and only the candidates' rows are read; longer lists and k > 128
+    run score_topk on the gathered sub-table. Empty candidates give all padding."""
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
     nu, d = eu.shape
     ni = ei.shape[0]
@@ -625,6 +718,31 @@ def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
         raise ValueError(f"exclusion rows {excl.n_rows} != users {nu}")
     ids = _user_ids(users, nu, eu.device)
     nb = int(ids.numel())
+    if items is not None:
+        cand = item_candidates(items, ni, eu.device)
+        nc = int(cand.numel())
+        if nc == 0 or nb == 0:
+            return _padding(nb, k, eu.device)
+        if nb > ITEMS_BATCH_MAX_USERS or k > BATCH_K_MAX:
+            return _score_topk_gathered(eu[ids], ei, cand, k,
+                                        excl.take(ids) if excl is not None else None,
+                                        mask_value)
+        if k < 1:
+            raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
+        if excl is not None and excl.col.numel() == 0:
+            excl = None  # (an empty tensor has no pointer to pass)
+        val = torch.empty((nb, k), dtype=torch.float32, device=eu.device)
+        idx = torch.empty((nb, k), dtype=torch.int64, device=eu.device)
+        ws_bytes = N.lib().lg_score_topk_batch_items_ws_bytes(min(nb, ITEMS_CALL_USERS), nc, d, k)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=eu.device)
+        for b0 in range(0, nb, ITEMS_CALL_USERS):
+            b1 = min(nb, b0 + ITEMS_CALL_USERS)
+            N.check(N.lib().lg_score_topk_batch_items_f32(
+                N.ptr(eu), N.ptr(ei), N.ptr(ids[b0:b1]), b1 - b0, nu, ni, N.ptr(cand), nc, d,
+                N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+                float(mask_value), k, N.ptr(val[b0:b1]), N.ptr(idx[b0:b1]), N.ptr(ws), ws_bytes,
+                N.stream_handle(eu.device)), "lg_score_topk_batch_items_f32")
+        return val, idx
     if nb == 0 or nb > BATCH_MAX_USERS or k > BATCH_K_MAX:
         return score_topk(eu[ids], ei, k, excl.take(ids) if excl is not None else None,
                           mask_value)

@@ -12,7 +12,10 @@ slabs); larger k raises.
 
 recommendForUsers is the request form: the same lists for a few user ids only, through
 ops.score_topk_users (lg_score_topk_batch_f32 for short lists: no rows gathered, no other
-user's scores computed).
+user's scores computed). With items= it ranks a candidate item set only (the in-stock items,
+one category, a retrieval stage's output): lg_score_topk_batch_items_f32 for short lists, which
+gathers nothing and reads only the candidates' rows. recommendForAllUser keeps the
+reference's signature.
 """
 import numpy as np
 import pandas as pd
@@ -45,14 +48,15 @@ def buildGraph(user_num: int, item_num: int, rating_df: pd.DataFrame,
 
 
 def topk_for_all_users(model, user_num: int, item_num: int, train_edge_index,
-                       val_edge_index, k: int):
-    """Device result of recommendForAllUser: (scores [U,k] fp32, items [U,k] int64)."""
+                       val_edge_index, k: int, items=None):
+    """Device result of recommendForAllUser: (scores [U,k] fp32, items [U,k] int64). items:
+    rank only a candidate item set (ops.item_candidates' forms; real item ids come back)."""
     w_u = model.users_emb.weight.detach()
     dev = gpu_device(w_u)
     eu = w_u.to(dev, torch.float32).contiguous()
     ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
     excl = exclusion_from_coo(user_num, item_num, train_edge_index, val_edge_index, device=dev)
-    return ops.score_topk(eu, ei, k, excl, mask_value=float(-(1 << 10)))
+    return ops.score_topk(eu, ei, k, excl, mask_value=float(-(1 << 10)), items=items)
 
 
 def recommendForAllUser(model, user_num: int, item_num: int,
@@ -67,26 +71,31 @@ def recommendForAllUser(model, user_num: int, item_num: int,
 
 
 def topk_for_users(model, user_ids, user_num: int, item_num: int, train_edge_index,
-                   val_edge_index, k: int):
+                   val_edge_index, k: int, items=None):
     """Device result of recommendForUsers: (scores [B,k] fp32, items [B,k] int64), row j =
     topk_for_all_users' row user_ids[j] (ops.score_topk_users: no score row of any other
-    user is computed)."""
+    user is computed). items: rank only a candidate item set (ops.item_candidates' forms;
+    short lists run lg_score_topk_batch_items_f32, which reads the candidates' rows only)."""
     w_u = model.users_emb.weight.detach()
     dev = gpu_device(w_u)
     eu = w_u.to(dev, torch.float32).contiguous()
     ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
     excl = exclusion_from_coo(user_num, item_num, train_edge_index, val_edge_index, device=dev)
-    return ops.score_topk_users(eu, ei, user_ids, k, excl, mask_value=float(-(1 << 10)))
+    return ops.score_topk_users(eu, ei, user_ids, k, excl, mask_value=float(-(1 << 10)),
+                                items=items)
 
 
 def recommendForUsers(model, user_ids, user_num: int, item_num: int,
                       train_edge_index: torch.Tensor, val_edge_index: torch.Tensor,
-                      test_edge_index: torch.Tensor, k: int) -> dict:
+                      test_edge_index: torch.Tensor, k: int, items=None) -> dict:
     """{uid: top-k items} for the given user ids only: the matching entries of
     recommendForAllUser (same -1024 mask, same lists). Writes no file. An id outside
-    [0, user_num) raises ValueError."""
+    [0, user_num) raises ValueError. items: recommend only from a candidate item set (ids, a
+    bool mask over the items, or a strictly ascending device tensor: ops.item_candidates); a
+    user with fewer than k candidates that can rank gets a shorter list."""
     ids = [int(u) for u in torch.as_tensor(user_ids).reshape(-1).tolist()]
-    _, idx = topk_for_users(model, ids, user_num, item_num, train_edge_index, val_edge_index, k)
+    _, idx = topk_for_users(model, ids, user_num, item_num, train_edge_index, val_edge_index, k,
+                            items=items)
     rows = topk_to_dict(idx)
     return {u: rows[j] for j, u in enumerate(ids)}
 
