@@ -23,17 +23,22 @@
 // tree over the waves. Every list order is total (item ids are distinct), so the result does
 // not depend on how the items were divided.
 //
+// The host side behind the stream is shared with K2i (csrc/topk_items.hip) through
+// batch_lists.h: the grid plan, the workspace bound and split, the argument checks. This file
+// holds the one definition of k_topk_batch_merge, of its launcher launch_batch_merge and of
+// device_cus. The workgroup tail of the scoring kernel (the pairwise tree and the store) is
+// the same text in both kernels: as one inlined function it kept every register count but
+// not hipcc's instruction stream, and missed the timing rule (CHANGELOG.md).
+//
 // LDS per workgroup: WAVES NG M x 8 KiB of lists; WAVES = min(4, 16 / (NG M)) keeps that within
 // 128 KiB (one workgroup per CU at NG M = 16, two where the lists take <= 64 KiB).
-#include "common.h"
+#include "batch_lists.h"
 #include "score_stream.h"
 
 namespace lg {
 namespace {
 
-constexpr int kBatchMax = 64;     // users per call
-constexpr int kMaxBlocks = 512;   // workgroups of the scoring grid: partial lists per user
-constexpr int kMergeWaves = 16;   // waves of k_topk_batch_merge's workgroup (one per user)
+constexpr int kBatchMax = 64;  // users per call
 
 // One wave: all the request's users (NG groups of 16; slot b = 16 g + (lane & 15) is row b of
 // the request), the items [w ipw, (w + 1) ipw) of the catalog, w = the wave's index in the grid.
@@ -344,24 +349,9 @@ __global__ __launch_bounds__(64 * kMergeWaves) void k_topk_batch_merge(
   }
 }
 
-int batch_cap_m(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }
 int batch_groups(int64_t n_batch) { return n_batch <= 16 ? 1 : (n_batch <= 32 ? 2 : 4); }
 // waves per workgroup: the lists (NG M x 8 KiB per wave) within 128 KiB
 int batch_waves(int ng, int m) { return ng * m >= 16 ? 1 : (ng * m >= 8 ? 2 : 4); }
-
-// compute units of the current device (cached per device ordinal)
-int device_cus() {
-  static int cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 0;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
 
 template <int D, int NG, int M>
 void launch_batch(int blocks, const float *eu, const float *ei, const int64_t *user_ids,
@@ -397,16 +387,12 @@ void dispatch_batch(int ng, int m, int blocks, const float *eu, const float *ei,
 
 using namespace lg;
 
-// One partial list per (workgroup, user): the grid never has more than kMaxBlocks workgroups,
-// nor more than one per 16-item tile. (The bound does not depend on the device.)
 extern "C" size_t lg_score_topk_batch_ws_bytes(int64_t n_batch, int64_t n_items, int32_t dim,
                                                int32_t k) {
   if (n_batch < 1 || n_batch > kBatchMax || n_items < 1 || n_items >= 0x7fffffff || k < 1 ||
       k > 128 || !(dim == 32 || dim == 64 || dim == 128))
     return 0;
-  const int64_t tiles = (n_items + 15) / 16;
-  const int64_t lists = tiles < kMaxBlocks ? tiles : kMaxBlocks;
-  return (size_t)lists * (size_t)n_batch * (size_t)k * (sizeof(float) + sizeof(int32_t));
+  return list_ws_bytes(n_items, n_batch, k);
 }
 
 extern "C" int lg_score_topk_batch_f32(const float *eu, const float *ei, const int64_t *user_ids,
@@ -415,51 +401,58 @@ extern "C" int lg_score_topk_batch_f32(const float *eu, const float *ei, const i
                                        const int32_t *ex_col, float mask_value, int32_t k,
                                        float *out_val, int64_t *out_idx, void *ws,
                                        size_t ws_bytes, lg_stream_t stream) {
-  LG_REQUIRE(eu && ei && out_val && out_idx, "lg_score_topk_batch_f32: null pointer");
-  LG_REQUIRE(n_batch >= 1 && n_batch <= kBatchMax,
-             "lg_score_topk_batch_f32: n_batch=%lld not in [1,%d]", (long long)n_batch, kBatchMax);
-  LG_REQUIRE(n_table_users >= 1, "lg_score_topk_batch_f32: n_table_users must be >= 1");
-  LG_REQUIRE(n_items > 0 && n_items < 0x7fffffff,
-             "lg_score_topk_batch_f32: n_items must be in [1, 2^31-1)");
-  LG_REQUIRE(dim == 32 || dim == 64 || dim == 128,
-             "lg_score_topk_batch_f32: dim %d not in {32,64,128}", dim);
-  LG_REQUIRE(k >= 1 && k <= 128, "lg_score_topk_batch_f32: k=%d not in [1,128]", k);
-  LG_REQUIRE(!ex_rowptr == !ex_col,
-             "lg_score_topk_batch_f32: ex_rowptr/ex_col must both be set");
-  const size_t need = lg_score_topk_batch_ws_bytes(n_batch, n_items, dim, k);
-  if (!ws || ws_bytes < need) {
-    set_error("lg_score_topk_batch_f32: workspace %zu < %zu bytes", ws_bytes, need);
-    return LG_ERR_WORKSPACE;
-  }
+  const char *me = "lg_score_topk_batch_f32";
+  const int st0 = check_list_args(me, eu && ei && out_val && out_idx, n_batch, kBatchMax,
+                                  n_table_users, n_items, dim, k, ex_rowptr, ex_col, ws, ws_bytes,
+                                  lg_score_topk_batch_ws_bytes(n_batch, n_items, dim, k));
+  if (st0 != LG_OK) return st0;
   const int cus = device_cus();
   if (cus <= 0) {
-    set_error("lg_score_topk_batch_f32: no device");
+    set_error("%s: no device", me);
     return LG_ERR_ARG;
   }
-  const int ng = batch_groups(n_batch), m = batch_cap_m(k), waves = batch_waves(ng, m);
-  // a grid that fills the device: two workgroups per CU where the lists take <= 64 KiB, else
-  // one; at least one 16-item tile per wave; the tiles divided evenly over its waves
-  const int64_t tiles = (n_items + 15) / 16;
-  int64_t blocks = (int64_t)cus * (waves * ng * m <= 8 ? 2 : 1);
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  if (blocks > (tiles + waves - 1) / waves) blocks = (tiles + waves - 1) / waves;
-  const int64_t ipw = (tiles + blocks * waves - 1) / (blocks * waves) * 16;
-  blocks = ((n_items + ipw - 1) / ipw + waves - 1) / waves;  // (no workgroup without items)
-  float *part_val = (float *)ws;
-  int32_t *part_idx = (int32_t *)((char *)ws + (size_t)blocks * n_batch * k * sizeof(float));
+  const int ng = batch_groups(n_batch), m = list_cap_m(k), waves = batch_waves(ng, m);
+  const ListGrid grid = plan_list_grid(n_items, cus, waves, waves * ng * m);
+  const int64_t blocks = grid.blocks, ipw = grid.per_wave;
+  const ListParts part = split_list_ws(ws, blocks, n_batch, k);
   hipStream_t s = (hipStream_t)stream;
   switch (dim) {
-    case 32: dispatch_batch<32>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part_val, part_idx, s); break;
-    case 64: dispatch_batch<64>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part_val, part_idx, s); break;
-    default: dispatch_batch<128>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part_val, part_idx, s); break;
+    case 32: dispatch_batch<32>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part.val, part.idx, s); break;
+    case 64: dispatch_batch<64>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part.val, part.idx, s); break;
+    default: dispatch_batch<128>(ng, m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, n_items, ex_rowptr, ex_col, mask_value, k, ipw, out_val, out_idx, part.val, part.idx, s); break;
   }
-  int st = launch_status("lg_score_topk_batch_f32");
+  const int st = launch_status(me);
   if (st != LG_OK || blocks == 1) return st;
+  return launch_batch_merge(part.val, part.idx, (int)n_batch, k, (int)blocks, out_val, out_idx, s,
+                            "lg_score_topk_batch_f32(merge)");
+}
+
+namespace lg {
+
+// (behind the entry: the kernels are emitted in the order of their first launch in this file)
+int device_cus() {
+  static int cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
+int launch_batch_merge(const float *part_val, const int32_t *part_idx, int n_batch, int k,
+                       int n_lists, float *out_val, int64_t *out_idx, hipStream_t s,
+                       const char *what) {
   if (k <= 64)
     k_topk_batch_merge<2><<<dim3((unsigned)n_batch), dim3(64 * kMergeWaves), 0, s>>>(
-        part_val, part_idx, (int)n_batch, k, (int)blocks, out_val, out_idx);
+        part_val, part_idx, n_batch, k, n_lists, out_val, out_idx);
   else
     k_topk_batch_merge<4><<<dim3((unsigned)n_batch), dim3(64 * kMergeWaves), 0, s>>>(
-        part_val, part_idx, (int)n_batch, k, (int)blocks, out_val, out_idx);
-  return launch_status("lg_score_topk_batch_f32(merge)");
+        part_val, part_idx, n_batch, k, n_lists, out_val, out_idx);
+  return launch_status(what);
 }
+
+}  // namespace lg

@@ -14,9 +14,10 @@
 // It is K2b (csrc/topk_batch.hip) with the division turned onto candidate POSITIONS: wave w of
 // the grid scores the positions [w ppw, (w + 1) ppw) of item_ids, ppw a multiple of 16. One
 // user group (n_batch <= 16) per wave, one list per user in LDS (CAP = 64 M entries), the
-// lazy exclusion of score_stream.h, the pairwise merge of a workgroup's waves, one partial
-// list per (workgroup, user), k_topk_items_merge (k_topk_batch_merge's text) for the final
-// lists. What differs from K2b's stream:
+// lazy exclusion of score_stream.h, the pairwise merge of a workgroup's waves (K2b's tail
+// text, see there), one partial list per (workgroup, user), and on the host K2b's own code
+// through batch_lists.h: the grid plan, the workspace bound and split, the argument checks and
+// k_topk_batch_merge (launch_batch_merge) for the final lists. What differs is the stream:
 //
 //   * The A tiles are row gathers: lane (ul, gq) of tile t reads piece gq of row
 //     item_ids[p0 + 16 t + ul] by a global load with a 64-bit address (the table may pass
@@ -35,7 +36,7 @@
 //     access.
 //
 // LDS per workgroup: 4 waves x 16 users x M x 512 B of lists = 32 / 64 / 128 KiB.
-#include "common.h"
+#include "batch_lists.h"
 #include "score_stream.h"
 
 namespace lg {
@@ -43,8 +44,6 @@ namespace {
 
 constexpr int kItemsBatchMax = 16;  // users per call: one group of 16 per wave
 constexpr int kItemsWaves = 4;      // waves per workgroup
-constexpr int kMaxBlocks = 512;     // workgroups of the scoring grid: partial lists per user
-constexpr int kMergeWaves = 16;     // waves of k_topk_items_merge's workgroup (one per user)
 
 template <int D, int M>
 __global__ __launch_bounds__(64 * kItemsWaves) void k_score_topk_items(
@@ -274,90 +273,6 @@ __global__ __launch_bounds__(64 * kItemsWaves) void k_score_topk_items(
   }
 }
 
-// k_topk_batch_merge's text (csrc/topk_batch.hip, where it is private to K2b's file): merge
-// the R partial lists of user blockIdx.x (each sorted, at most k entries, padded with id -1);
-// wave w of the 16 takes the lists w, w + 16, .., then the waves merge pairwise in LDS.
-template <int M>
-__global__ __launch_bounds__(64 * kMergeWaves) void k_topk_items_merge(
-    const float *__restrict__ part_val, const int32_t *__restrict__ part_idx, int n_batch,
-    int k, int n_lists, float *__restrict__ out_val, int64_t *__restrict__ out_idx) {
-  constexpr int CAP = 64 * M;
-  __shared__ float cs[kMergeWaves][CAP];
-  __shared__ int ci[kMergeWaves][CAP];
-  __shared__ int ncs[kMergeWaves];
-  const int wave = threadIdx.x / 64;
-  const int lane = lane_id();
-  const int b = blockIdx.x;
-  int cnt = 0;
-  float tau = neg_inf<float>();
-  int tau_id = kPadId;
-  for (int r = wave; r < n_lists; r += kMergeWaves) {
-    const int64_t base = ((int64_t)r * n_batch + b) * k;
-    for (int e0 = 0; e0 < k; e0 += 64) {
-      const int e = e0 + lane;
-      float v = neg_inf<float>();
-      int id = -1;
-      if (e < k) {
-        v = part_val[base + e];
-        id = part_idx[base + e];
-      }
-      const bool cand = id >= 0 && before(v, id, tau, tau_id);
-      const uint64_t bal = __ballot(cand);
-      const int pos = cnt + __popcll(bal & lanemask_lt());
-      if (cand) {
-        cs[wave][pos] = v;
-        ci[wave][pos] = id;
-      }
-      cnt += __popcll(bal);
-      if (cnt > CAP - 64) {
-        wave_sync();
-        cnt = wave_compact<float, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-      }
-    }
-  }
-  wave_sync();
-  cnt = wave_compact<float, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-  if (lane == 0) ncs[wave] = cnt;
-  for (int s = 1; s < kMergeWaves; s <<= 1) {
-    __syncthreads();
-    if ((wave & (2 * s - 1)) == 0) {
-      const int n0 = ncs[wave];
-      const int n1 = ncs[wave + s];
-      if (n1 > 0) {  // (wave-uniform; n0 + n1 <= 2k <= CAP)
-        for (int e = lane; e < n1; e += 64) {
-          cs[wave][n0 + e] = cs[wave + s][e];
-          ci[wave][n0 + e] = ci[wave + s][e];
-        }
-        wave_sync();
-        const int nc = wave_compact<float, M>(cs[wave], ci[wave], n0 + n1, k, tau, tau_id);
-        if (lane == 0) ncs[wave] = nc;
-      }
-    }
-  }
-  __syncthreads();
-  const int nc = ncs[0];
-  for (int e = threadIdx.x; e < k; e += 64 * kMergeWaves) {
-    out_val[(int64_t)b * k + e] = e < nc ? cs[0][e] : neg_inf<float>();
-    out_idx[(int64_t)b * k + e] = e < nc ? ci[0][e] : -1;
-  }
-}
-
-int items_cap_m(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }
-
-// compute units of the current device (cached per device ordinal)
-int device_cus() {
-  static int cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 0;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
 template <int D>
 void dispatch_items(int m, int blocks, const float *eu, const float *ei, const int64_t *user_ids,
                     int n_batch, int64_t n_table_users, int n_items, const int32_t *item_ids,
@@ -379,16 +294,12 @@ void dispatch_items(int m, int blocks, const float *eu, const float *ei, const i
 
 using namespace lg;
 
-// One partial list per (workgroup, user): the grid never has more than kMaxBlocks workgroups,
-// nor more than one per 16-candidate tile. (The bound does not depend on the device.)
 extern "C" size_t lg_score_topk_batch_items_ws_bytes(int64_t n_batch, int64_t n_cand,
                                                      int32_t dim, int32_t k) {
   if (n_batch < 1 || n_batch > kItemsBatchMax || n_cand < 1 || n_cand >= 0x7fffffff || k < 1 ||
       k > 128 || !(dim == 32 || dim == 64 || dim == 128))
     return 0;
-  const int64_t tiles = (n_cand + 15) / 16;
-  const int64_t lists = tiles < kMaxBlocks ? tiles : kMaxBlocks;
-  return (size_t)lists * (size_t)n_batch * (size_t)k * (sizeof(float) + sizeof(int32_t));
+  return list_ws_bytes(n_cand, n_batch, k);
 }
 
 extern "C" int lg_score_topk_batch_items_f32(
@@ -396,56 +307,32 @@ extern "C" int lg_score_topk_batch_items_f32(
     int64_t n_table_users, int64_t n_items, const int32_t *item_ids, int64_t n_cand, int32_t dim,
     const int64_t *ex_rowptr, const int32_t *ex_col, float mask_value, int32_t k, float *out_val,
     int64_t *out_idx, void *ws, size_t ws_bytes, lg_stream_t stream) {
-  LG_REQUIRE(eu && ei && item_ids && out_val && out_idx,
-             "lg_score_topk_batch_items_f32: null pointer");
-  LG_REQUIRE(n_batch >= 1 && n_batch <= kItemsBatchMax,
-             "lg_score_topk_batch_items_f32: n_batch=%lld not in [1,%d]", (long long)n_batch,
-             kItemsBatchMax);
-  LG_REQUIRE(n_table_users >= 1, "lg_score_topk_batch_items_f32: n_table_users must be >= 1");
-  LG_REQUIRE(n_items > 0 && n_items < 0x7fffffff,
-             "lg_score_topk_batch_items_f32: n_items must be in [1, 2^31-1)");
-  LG_REQUIRE(n_cand >= 1 && n_cand <= n_items,
-             "lg_score_topk_batch_items_f32: n_cand=%lld not in [1, n_items=%lld]",
+  const char *me = "lg_score_topk_batch_items_f32";
+  LG_REQUIRE(n_cand >= 1 && n_cand <= n_items, "%s: n_cand=%lld not in [1, n_items=%lld]", me,
              (long long)n_cand, (long long)n_items);
-  LG_REQUIRE(dim == 32 || dim == 64 || dim == 128,
-             "lg_score_topk_batch_items_f32: dim %d not in {32,64,128}", dim);
-  LG_REQUIRE(k >= 1 && k <= 128, "lg_score_topk_batch_items_f32: k=%d not in [1,128]", k);
-  LG_REQUIRE(!ex_rowptr == !ex_col,
-             "lg_score_topk_batch_items_f32: ex_rowptr/ex_col must both be set");
-  const size_t need = lg_score_topk_batch_items_ws_bytes(n_batch, n_cand, dim, k);
-  if (!ws || ws_bytes < need) {
-    set_error("lg_score_topk_batch_items_f32: workspace %zu < %zu bytes", ws_bytes, need);
-    return LG_ERR_WORKSPACE;
-  }
+  const int st0 = check_list_args(me, eu && ei && item_ids && out_val && out_idx, n_batch,
+                                  kItemsBatchMax, n_table_users, n_items, dim, k, ex_rowptr,
+                                  ex_col, ws, ws_bytes,
+                                  lg_score_topk_batch_items_ws_bytes(n_batch, n_cand, dim, k));
+  if (st0 != LG_OK) return st0;
   const int cus = device_cus();
   if (cus <= 0) {
-    set_error("lg_score_topk_batch_items_f32: no device");
+    set_error("%s: no device", me);
     return LG_ERR_ARG;
   }
-  const int m = items_cap_m(k), waves = kItemsWaves;
-  // K2b's grid over the candidate positions: two workgroups per CU where the lists take
-  // <= 64 KiB, else one; at least one 16-candidate tile per wave; the tiles divided evenly
-  const int64_t tiles = (n_cand + 15) / 16;
-  int64_t blocks = (int64_t)cus * (waves * m <= 8 ? 2 : 1);
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  if (blocks > (tiles + waves - 1) / waves) blocks = (tiles + waves - 1) / waves;
-  const int64_t ppw = (tiles + blocks * waves - 1) / (blocks * waves) * 16;
-  blocks = ((n_cand + ppw - 1) / ppw + waves - 1) / waves;  // (no workgroup without candidates)
-  float *part_val = (float *)ws;
-  int32_t *part_idx = (int32_t *)((char *)ws + (size_t)blocks * n_batch * k * sizeof(float));
+  // K2b's grid over the candidate positions
+  const int m = list_cap_m(k), waves = kItemsWaves;
+  const ListGrid grid = plan_list_grid(n_cand, cus, waves, waves * m);
+  const int64_t blocks = grid.blocks, ppw = grid.per_wave;
+  const ListParts part = split_list_ws(ws, blocks, n_batch, k);
   hipStream_t s = (hipStream_t)stream;
   switch (dim) {
-    case 32: dispatch_items<32>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part_val, part_idx, s); break;
-    case 64: dispatch_items<64>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part_val, part_idx, s); break;
-    default: dispatch_items<128>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part_val, part_idx, s); break;
+    case 32: dispatch_items<32>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part.val, part.idx, s); break;
+    case 64: dispatch_items<64>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part.val, part.idx, s); break;
+    default: dispatch_items<128>(m, (int)blocks, eu, ei, user_ids, (int)n_batch, n_table_users, (int)n_items, item_ids, n_cand, ex_rowptr, ex_col, mask_value, k, ppw, out_val, out_idx, part.val, part.idx, s); break;
   }
-  int st = launch_status("lg_score_topk_batch_items_f32");
+  const int st = launch_status(me);
   if (st != LG_OK || blocks == 1) return st;
-  if (k <= 64)
-    k_topk_items_merge<2><<<dim3((unsigned)n_batch), dim3(64 * kMergeWaves), 0, s>>>(
-        part_val, part_idx, (int)n_batch, k, (int)blocks, out_val, out_idx);
-  else
-    k_topk_items_merge<4><<<dim3((unsigned)n_batch), dim3(64 * kMergeWaves), 0, s>>>(
-        part_val, part_idx, (int)n_batch, k, (int)blocks, out_val, out_idx);
-  return launch_status("lg_score_topk_batch_items_f32(merge)");
+  return launch_batch_merge(part.val, part.idx, (int)n_batch, k, (int)blocks, out_val, out_idx, s,
+                            "lg_score_topk_batch_items_f32(merge)");
 }

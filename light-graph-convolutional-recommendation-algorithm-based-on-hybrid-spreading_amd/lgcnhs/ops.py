@@ -591,19 +591,30 @@ BATCH_K_MAX = 128      # its largest k
 BATCH_MAX_USERS = 16
 
 
-def batch_topk_grid(n_batch: int, n_items: int, k: int, device) -> tuple:
+def _list_grid(n: int, cus, waves: int, ng: int, k: int, device) -> tuple:
+    """(workgroups, waves per workgroup, items or candidate positions per wave) of the scoring
+    launch of lg_score_topk_batch_f32 / lg_score_topk_batch_items_f32 on a device of `cus`
+    compute units, default `device`'s (plan_list_grid of csrc/batch_lists.h, restated): n
+    entries in 16-entry tiles divided evenly over every wave of a grid that fills the device;
+    a workgroup's lists are waves x ng user groups x M (k) units of 8 KiB."""
+    if cus is None:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+    m = 1 if k <= 32 else (2 if k <= 64 else 4)
+    tiles = (n + 15) // 16
+    blocks = min(512, cus * (2 if waves * ng * m <= 8 else 1), -(-tiles // waves))
+    per_wave = -(-tiles // (blocks * waves)) * 16
+    busy = -(-n // per_wave)  # waves with entries
+    return -(-busy // waves), waves, per_wave
+
+
+def batch_topk_grid(n_batch: int, n_items: int, k: int, device, cus: int | None = None) -> tuple:
     """(workgroups, waves per workgroup, items per wave) of lg_score_topk_batch_f32's scoring
-    launch (the host code of csrc/topk_batch.hip, restated): every wave holds all n_batch users
-    and scores items_per_wave consecutive items."""
+    launch: every wave holds all n_batch users and scores items_per_wave consecutive items.
+    cus: the compute units to plan for (default: `device`'s)."""
     ng = 1 if n_batch <= 16 else (2 if n_batch <= 32 else 4)
     m = 1 if k <= 32 else (2 if k <= 64 else 4)
     waves = 1 if ng * m >= 16 else (2 if ng * m >= 8 else 4)
-    cus = torch.cuda.get_device_properties(device).multi_processor_count
-    tiles = (n_items + 15) // 16
-    blocks = min(512, cus * (2 if waves * ng * m <= 8 else 1), -(-tiles // waves))
-    ipw = -(-tiles // (blocks * waves)) * 16
-    busy = -(-n_items // ipw)  # waves with items
-    return -(-busy // waves), waves, ipw
+    return _list_grid(n_items, cus, waves, ng, k, device)
 
 
 def _user_ids(users, n_users: int, device) -> torch.Tensor:
@@ -659,18 +670,11 @@ def item_candidates(items, n_items: int, device) -> torch.Tensor:
     return t.to(torch.int32).to(device)
 
 
-def items_topk_grid(n_batch: int, n_cand: int, k: int, device) -> tuple:
+def items_topk_grid(n_batch: int, n_cand: int, k: int, device, cus: int | None = None) -> tuple:
     """(workgroups, waves per workgroup, candidate positions per wave) of
-    lg_score_topk_batch_items_f32's scoring launch (the host code of csrc/topk_items.hip,
-    restated): batch_topk_grid's arithmetic for one user group over n_cand positions."""
-    m = 1 if k <= 32 else (2 if k <= 64 else 4)
-    waves = 4
-    cus = torch.cuda.get_device_properties(device).multi_processor_count
-    tiles = (n_cand + 15) // 16
-    blocks = min(512, cus * (2 if waves * m <= 8 else 1), -(-tiles // waves))
-    ppw = -(-tiles // (blocks * waves)) * 16
-    busy = -(-n_cand // ppw)  # waves with candidates
-    return -(-busy // waves), waves, ppw
+    lg_score_topk_batch_items_f32's scoring launch: batch_topk_grid's arithmetic for one user
+    group and 4 waves over n_cand positions."""
+    return _list_grid(n_cand, cus, 4, 1, k, device)
 
 
 def _padding(n_rows: int, k: int, device):
@@ -689,6 +693,27 @@ def _score_topk_gathered(eu, ei, cand, k, excl, mask_value, **kw):
         ex = None  # (no excluded candidate at all: an empty tensor has no pointer to pass)
     v, i = score_topk(eu, ei[c64], k, ex, mask_value, **kw)
     return v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
+
+
+def _topk_lists(entry: str, chunk: int, eu, ei, ids, k, excl, mask_value, cand=None):
+    """score_topk_users through the C entry `entry`_f32 (lg_score_topk_batch or
+    lg_score_topk_batch_items, the latter with its candidates `cand`): `chunk` users per call,
+    one workspace of `entry`_ws_bytes for a full chunk."""
+    lib, dev = N.lib(), eu.device
+    (nu, d), ni, nb = eu.shape, ei.shape[0], int(ids.numel())
+    n, mid = (ni, ()) if cand is None else (int(cand.numel()), (N.ptr(cand), int(cand.numel())))
+    val = torch.empty((nb, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((nb, k), dtype=torch.int64, device=dev)
+    ws_bytes = getattr(lib, entry + "_ws_bytes")(min(nb, chunk), n, d, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    for b0 in range(0, nb, chunk):
+        b1 = min(nb, b0 + chunk)
+        N.check(getattr(lib, entry + "_f32")(
+            N.ptr(eu), N.ptr(ei), N.ptr(ids[b0:b1]), b1 - b0, nu, ni, *mid, d,
+            N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+            float(mask_value), k, N.ptr(val[b0:b1]), N.ptr(idx[b0:b1]), N.ptr(ws), ws_bytes,
+            N.stream_handle(dev)), entry + "_f32")
+    return val, idx
 
 
 def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
@@ -731,35 +756,14 @@ def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
             raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
         if excl is not None and excl.col.numel() == 0:
             excl = None  # (an empty tensor has no pointer to pass)
-        val = torch.empty((nb, k), dtype=torch.float32, device=eu.device)
-        idx = torch.empty((nb, k), dtype=torch.int64, device=eu.device)
-        ws_bytes = N.lib().lg_score_topk_batch_items_ws_bytes(min(nb, ITEMS_CALL_USERS), nc, d, k)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=eu.device)
-        for b0 in range(0, nb, ITEMS_CALL_USERS):
-            b1 = min(nb, b0 + ITEMS_CALL_USERS)
-            N.check(N.lib().lg_score_topk_batch_items_f32(
-                N.ptr(eu), N.ptr(ei), N.ptr(ids[b0:b1]), b1 - b0, nu, ni, N.ptr(cand), nc, d,
-                N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
-                float(mask_value), k, N.ptr(val[b0:b1]), N.ptr(idx[b0:b1]), N.ptr(ws), ws_bytes,
-                N.stream_handle(eu.device)), "lg_score_topk_batch_items_f32")
-        return val, idx
+        return _topk_lists("lg_score_topk_batch_items", ITEMS_CALL_USERS, eu, ei, ids, k, excl,
+                           mask_value, cand)
     if nb == 0 or nb > BATCH_MAX_USERS or k > BATCH_K_MAX:
         return score_topk(eu[ids], ei, k, excl.take(ids) if excl is not None else None,
                           mask_value)
     if k < 1:
         raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
-    val = torch.empty((nb, k), dtype=torch.float32, device=eu.device)
-    idx = torch.empty((nb, k), dtype=torch.int64, device=eu.device)
-    ws_bytes = N.lib().lg_score_topk_batch_ws_bytes(min(nb, BATCH_CALL_USERS), ni, d, k)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=eu.device)
-    for b0 in range(0, nb, BATCH_CALL_USERS):
-        b1 = min(nb, b0 + BATCH_CALL_USERS)
-        N.check(N.lib().lg_score_topk_batch_f32(
-            N.ptr(eu), N.ptr(ei), N.ptr(ids[b0:b1]), b1 - b0, nu, ni, d,
-            N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
-            float(mask_value), k, N.ptr(val[b0:b1]), N.ptr(idx[b0:b1]), N.ptr(ws), ws_bytes,
-            N.stream_handle(eu.device)), "lg_score_topk_batch_f32")
-    return val, idx
+    return _topk_lists("lg_score_topk_batch", BATCH_CALL_USERS, eu, ei, ids, k, excl, mask_value)
 
 
 def score_dense(eu: torch.Tensor, ei: torch.Tensor, excl: RowSets | None = None,

@@ -163,6 +163,46 @@ def test_catalog_just_past_one_round_of_waves(nb, k):
     _same_rows(v, i, ref, ids)
 
 
+def _half_excl(U, I, density, seed):
+    """_excl with rows for the even users only: about half the users have exclusion rows."""
+    rng = np.random.default_rng(seed)
+    n = int(U * I * density)
+    return O.exclusion_csr(U, I, (2 * rng.integers(0, U // 2, n), rng.integers(0, I, n)))
+
+
+# (R partial lists, tight): tight = the last workgroup has one wave with one item and its other
+# waves empty (R >= 2)
+_LIST_CASES = [(R, False) for R in (1, 2, 16, 17, 33)] + [(R, True) for R in (2, 16, 17, 33)]
+
+
+@pytest.mark.parametrize("R,tight", _LIST_CASES)
+def test_partial_list_counts(R, tight):
+    """R workgroups = R partial lists per user, one 16-item tile per wave (the grid from
+    ops.batch_topk_grid, asserted): R = 1 writes the rows with no merge, 2 and 16 are the merge
+    kernel's tree alone, at 17 a merge wave takes two lists, at 33 three. tight: 16 waves - 1
+    items fewer, so the last workgroup's tree meets empty lists. B x k = {1, 16} x {20, 100}
+    (4 waves per workgroup; merge <2> and <4>), (32, 128) (2 waves: one tree step) and
+    (64, 128) (1 wave: no tree). Rows equal lg_score_topk_f32's bit for bit; every second user
+    has exclusion rows."""
+    from lgcnhs import ops
+    d = 32
+    eu = _tables(d)[0]
+    refs = {}
+    for nb, k in ((1, 20), (16, 20), (1, 100), (16, 100), (32, 128), (64, 128)):
+        waves = ops.batch_topk_grid(nb, 1 << 20, k, DEV)[1]
+        assert waves == {32: 2, 64: 1}.get(nb, 4)
+        I = 16 * waves * R - ((16 * waves - 1) if tight else 0)
+        assert ops.batch_topk_grid(nb, I, k, DEV) == (R, waves, 16)
+        if (I, k) not in refs:
+            ei = _emb(64 * 33, d, 61)[:I].contiguous().to(DEV)
+            ex = _rowsets(*_half_excl(U_TAB, I, 0.2, 62 + I), U_TAB, I)
+            refs[I, k] = ei, ex, ops.score_topk(eu, ei, k, ex, screen=False)
+        ei, ex, ref = refs[I, k]
+        ids = _ids(nb, 63 + nb)
+        v, i = _batch(eu, ei, ids, k, ex)
+        _same_rows(v, i, ref, ids, (R, tight, nb, k))
+
+
 @pytest.mark.parametrize("nb,k,I", [(16, 20, 300001), (64, 128, 300001)])
 def test_long_ranges_compact_mid_stream(nb, k, I):
     """Enough items per wave (~146 at 2,048 waves, ~1,172 at 256) that lists overflow and are

@@ -210,6 +210,40 @@ def test_candidates_just_past_one_round_of_waves(nb, k):
     _same_rows(v, i, ref, ids)
 
 
+# (R partial lists, tight): tight = the last workgroup has one wave with one candidate and three
+# empty waves (R >= 2)
+_LIST_CASES = [(R, False) for R in (1, 2, 16, 17, 33)] + [(R, True) for R in (2, 16, 17, 33)]
+
+
+@pytest.mark.parametrize("R,tight", _LIST_CASES)
+def test_partial_list_counts(R, tight):
+    """R workgroups = R partial lists per user, one 16-candidate tile per wave (the grid from
+    ops.items_topk_grid, asserted): R = 1 writes the rows with no merge, 2 and 16 are the merge
+    kernel's tree alone, at 17 a merge wave takes two lists, at 33 three. tight: 63 candidates
+    fewer, so the last workgroup's tree meets empty lists. Candidates = every third item;
+    B x k = {1, 16} x {20, 100} (merge <2> and <4>). Rows equal lg_score_topk_f32's on the
+    gathered sub-table bit for bit; every second user has exclusion rows."""
+    from lgcnhs import ops
+    d = 32
+    nc = 64 * R - (63 if tight else 0)
+    I = 3 * nc
+    cand = np.arange(0, I, 3, dtype=np.int32)
+    eu = _tables(d)[0]
+    ei = _emb(3 * 64 * 33, d, 61)[:I].contiguous().to(DEV)
+    rng = np.random.default_rng(62 + nc)
+    n = int(U_TAB * I * 0.2)
+    rp, col = O.exclusion_csr(U_TAB, I, (2 * rng.integers(0, U_TAB // 2, n),
+                                         rng.integers(0, I, n)))
+    ex = _rowsets(rp, col, U_TAB, I)
+    for k in (20, 100):
+        ref = _twin(eu, ei, rp, col, cand, k)
+        for nb in (1, 16):
+            assert ops.items_topk_grid(nb, nc, k, DEV) == (R, 4, 16)
+            ids = _ids(nb, 63 + nb)
+            v, i = _items(eu, ei, ids, cand, k, ex)
+            _same_rows(v, i, ref, ids, (R, tight, nb, k))
+
+
 @pytest.mark.parametrize("nb,k", [(16, 20), (16, 128)])
 def test_long_ranges_compact_mid_stream(nb, k):
     """Every second item of 300,001 (~150,000 candidates): enough positions per wave that lists

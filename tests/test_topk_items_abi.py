@@ -93,6 +93,26 @@ def test_ws_bytes_shape(lib):
         assert f(*bad) == 0, bad
 
 
+@pytest.mark.parametrize("cus", [1, 8, 64, 256, 304])
+def test_grid_plan_fits_the_workspace(lib, cus):
+    """The Python planner (ops.items_topk_grid on `cus` compute units) over catalog sizes around
+    the tile and wave counts and every B and k class: positions per wave a multiple of 16, the
+    grid covers n, no workgroup is empty, at most min(512, one per `waves` tiles) workgroups,
+    and their partial lists fit lg_score_topk_batch_items_ws_bytes -- the bound the split of the
+    workspace into values and ids rests on."""
+    from lgcnhs import ops
+    for n in (1, 15, 16, 17, 63, 64, 65, 1023, 8191, 8192, 8193, 10**6):
+        for nb in (1, 8, 16):
+            for k in (1, 32, 33, 64, 65, 128):
+                blocks, waves, per_wave = ops.items_topk_grid(nb, n, k, None, cus=cus)
+                what = (n, nb, k, blocks, waves, per_wave)
+                assert per_wave % 16 == 0 and per_wave > 0, what
+                assert blocks * waves * per_wave >= n, what
+                assert (blocks - 1) * waves * per_wave < n, what
+                assert 1 <= blocks <= min(512, -(-(-(-n // 16)) // waves)), what
+                assert blocks * nb * k * 8 <= lib.lg_score_topk_batch_items_ws_bytes(nb, n, 64, k), what
+
+
 def test_item_candidates_on_the_host():
     """ops.item_candidates: ids come back ascending and unique as int32; a bool mask gives its
     true positions; a bad id, a float or a mask of the wrong length raises before anything
