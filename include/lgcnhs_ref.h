@@ -1,6 +1,7 @@
 /*
  * lgcnhs_ref.h — test-reference entry points of the factored spreading (K3s), exported ONLY
- * by lib/liblgcnhs_ref.so (the same sources built with -DLG_REFERENCE_PATHS=1). The product
+ * by lib/liblgcnhs_ref.so (the product's objects with csrc/spread_ref.hip's in place of the
+ * walk's; that file includes the walk's source and defines these). The product
  * library lib/liblgcnhs.so does not carry them: they are the per-tile forms that the
  * product's group build (lg_spread_group_*) and fused walk (lg_spread_tile_resource_topk_f64)
  * replace, kept so the tests can check those bit for bit (tests/_ref_paths.py). Conventions

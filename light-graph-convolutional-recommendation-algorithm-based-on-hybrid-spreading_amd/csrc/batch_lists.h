@@ -5,7 +5,7 @@
 // (csrc/topk_batch.hip, the one device copy) merges a user's partial lists.
 //
 // - the grid plan, the workspace bound and its split, the argument checks of both entries
-// - device_cus, launch_batch_merge: defined once, in csrc/topk_batch.hip
+// - launch_batch_merge: defined once, in csrc/topk_batch.hip (as is common.h's device_cus)
 #pragma once
 
 #include "common.h"
@@ -17,9 +17,6 @@ constexpr int kMergeWaves = 16;  // waves of k_topk_batch_merge's workgroup (one
 
 // list capacity CAP = 64 M entries per (wave, user): 2k <= CAP for the pairwise merges
 inline int list_cap_m(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }
-
-// compute units of the current device (cached per device ordinal); 0: no device
-int device_cus();
 
 // Merge the n_lists partial lists of each of n_batch users (part_val / part_idx: list r of
 // user b at ((r n_batch + b) k), sorted, padded with id -1) into out_val / out_idx.

@@ -17,6 +17,9 @@ namespace lg {
 
 void set_error(const char *fmt, ...);
 int launch_status(const char *what);
+// compute units of the current device (cached per device ordinal); 0: no device
+// (defined in topk_batch.hip)
+int device_cus();
 
 constexpr int kWave = 64;
 

@@ -1,5 +1,5 @@
 // K4: top-K over dense fp64 rows (the spreading / LGCNHS recommendation) and the merge of
-// top-K lists for 128 < k <= 1024, gfx950.
+// top-K lists (lg_topk_lists_merge_f64, k <= 128; _wide_f64, k <= 1024), gfx950.
 //
 // Reference: model/SpreadMethod/recommend.py:31-50 and model/SpreadLightGCN/recommend.py: per
 // user argsort(F[u])[::-1], drop train|val items, [:k] -- any RECOMMEND["k"] -- with
@@ -201,8 +201,64 @@ static int check_rows_args(const char *who, int kmax, const RowsArgs &a) {
   return LG_OK;
 }
 
-// k_lists_merge_f64 of spread_tiled.hip with the list (k <= CAP / 2) in LDS: one wave per
-// row, NWB rows per block.
+// Merge n_lists sorted top-K lists per row ([n_lists][n_rows][k], index -1 = empty) into one
+// ([n_rows][k]): the item-range shards of a multi-GPU spreading run. One wave per row, the
+// candidate list in LDS (CAP = 64*M >= k + 64), compacted by the wave-wide bitonic sort.
+// (A twin of k_lists_merge_wide below: as one k_lists_merge<List, NWB> this one compiled to
+// another instruction order, k = 64 slower than the parent's spread: DESIGN.md.)
+template <int M>
+__global__ __launch_bounds__(256) void k_lists_merge_f64(const double *__restrict__ in_val,
+                                                         const int64_t *__restrict__ in_idx,
+                                                         int n_lists, int64_t n_rows, int k,
+                                                         double *__restrict__ out_val,
+                                                         int64_t *__restrict__ out_idx) {
+  constexpr int CAP = 64 * M;
+  __shared__ double cs[4][CAP];
+  __shared__ int ci[4][CAP];
+  const int wave = threadIdx.x / 64;
+  const int lane = lane_id();
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  if (row >= n_rows) return;
+  int cnt = 0;
+  double tau = neg_inf<double>();
+  int tau_id = kPadId;
+  for (int s = 0; s < n_lists; ++s) {
+    const int64_t base = ((int64_t)s * n_rows + row) * k;
+    for (int e0 = 0; e0 < k; e0 += 64) {
+      const int e = e0 + lane;
+      double v = neg_inf<double>();
+      int id = -1;
+      if (e < k) {
+        const int64_t x = in_idx[base + e];
+        if (x >= 0) {
+          v = in_val[base + e];
+          id = (int)x;
+        }
+      }
+      const bool cand = id >= 0 && before(v, id, tau, tau_id);
+      const uint64_t bal = __ballot(cand);
+      const int pos = cnt + __popcll(bal & lanemask_lt());
+      if (cand) {
+        cs[wave][pos] = v;
+        ci[wave][pos] = id;
+      }
+      cnt += __popcll(bal);
+      if (cnt > CAP - 64) {
+        wave_sync();
+        cnt = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
+      }
+    }
+  }
+  wave_sync();
+  const int nc = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
+  for (int e = lane; e < k; e += 64) {
+    out_val[row * k + e] = e < nc ? cs[wave][e] : neg_inf<double>();
+    out_idx[row * k + e] = e < nc ? ci[wave][e] : -1;
+  }
+}
+
+// k_lists_merge_f64 with the list (k <= CAP / 2) in LDS: one wave per row, NWB rows per
+// block.
 template <int CAP, int NWB>
 __global__ __launch_bounds__(64 * NWB) void k_lists_merge_wide(
     const double *__restrict__ in_val, const int64_t *__restrict__ in_idx, int n_lists,
@@ -292,6 +348,25 @@ extern "C" int lg_rows_topk_wide_f64(const double *F, int64_t ldf, int64_t n_row
   else if (k <= 512) launch_rows_topk<LdsList<512>, 4>(a);
   else launch_rows_topk<LdsList<1024>, 2>(a);
   return launch_status("lg_rows_topk_wide_f64");
+}
+
+extern "C" int lg_topk_lists_merge_f64(const double *in_val, const int64_t *in_idx,
+                                       int32_t n_lists, int64_t n_rows, int32_t k,
+                                       double *out_val, int64_t *out_idx, lg_stream_t stream) {
+  LG_REQUIRE(n_lists >= 1 && n_rows >= 0, "lg_topk_lists_merge_f64: bad sizes");
+  LG_REQUIRE(k >= 1 && k <= 128, "lg_topk_lists_merge_f64: k=%d not in [1,128]", k);
+  LG_REQUIRE(n_rows == 0 || (in_val && in_idx && out_val && out_idx),
+             "lg_topk_lists_merge_f64: NULL argument");
+  if (n_rows == 0) return LG_OK;
+  const dim3 grid((unsigned)((n_rows + 3) / 4));
+  hipStream_t s = (hipStream_t)stream;
+  if (k <= 64)
+    k_lists_merge_f64<2><<<grid, dim3(256), 0, s>>>(in_val, in_idx, n_lists, n_rows, k, out_val,
+                                                    out_idx);
+  else
+    k_lists_merge_f64<4><<<grid, dim3(256), 0, s>>>(in_val, in_idx, n_lists, n_rows, k, out_val,
+                                                    out_idx);
+  return launch_status("lg_topk_lists_merge_f64");
 }
 
 extern "C" int lg_topk_lists_merge_wide_f64(const double *in_val, const int64_t *in_idx,

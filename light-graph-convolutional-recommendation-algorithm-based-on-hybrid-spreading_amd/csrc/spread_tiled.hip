@@ -1,1212 +1,15 @@
-// K3s: factored hybrid spreading for catalogs whose I x I matrices do not fit (SURVEY.md §8
-// a9 "K3s", C5: 1M x 1M, 100M interactions -> general_W and W would be 8 TB each).
-//
-// Reference (dense numpy fp64, model/SpreadMethod/model.py):
-//   general_W = (A.T / k_u) @ A            :14-27
-//   W = general_W / (k_i^(1-l) (x) k_j^l)   :63-85   (den == 0 -> 1)
-//   F = A @ W                               :88-99
-//   F_new = G * F; per user argsort desc, drop train|val, [:k]
-//                       model/SpreadLightGCN/model.py:151, recommend.py:18-52
-//
-// Factored: W[i][j] = general_W[i][j] * ra_i * rb_j with ra = 1/alpha, rb = 1/beta (alpha_i =
-// k_i^(1-l), beta_j = k_j^l; a zero factor -> 1, the reference's den == 0 rule), so
-//   F[u][j] = rb_j * sum_{i in items(u)} ra_i * sum_{v in users(i) and users(j)} fl(1/k_v)
-//           = rb_j * sum over the 3-hop paths u -> i -> v -> j of fl(1/k_v) * ra_i.
-// The items are processed in column tiles [j0, j0 + T). Per tile:
-//   cursor   end[v] = first position of user v's (ascending) item row with item >= j0 + T;
-//            cur[v] (the previous tile's end) marks the first item >= j0, so
-//            items(v) inside the tile = user_items[cur[v] .. end[v])
-//   bound    bound[i] = sum_{v in users(i)} (end[v] - cur[v]) = the (user, item) pairs
-//            behind row i of W in the tile (its paths)
-//   rows     row i of general_W restricted to the tile, in the line format below
-//   walk     per user (one wave): the paths of its rows added into an LDS accumulator, then
-//            scaled by rb_j and either written out (F mode) or merged straight into the
-//            user's running top-K list (top-K mode: (G *) F, G = the fp32 e0 score chain,
-//            candidates screened by per-(user, 64-column chunk) score bounds).
-// Work: the rows pass costs sum_i deg(i) lookups + the 2-hop pairs once per tile (not per
-// user); the walk reads one 128-byte line per (user, item) and tile (~5e10 lines at C5) and
-// adds ~1e12 paths (one LDS atomic each); F never leaves LDS.
-//
-// Rounding: every path contributes fl(fl(1/k_v) * ra_i) (P rows) or fl(general_W[i][j] * ra_i)
-// (V rows); the sum order is the walk's (fixed: deterministic, but not the dense path's
-// ascending-i order), then one multiply by rb_j. Against the reference's
-// general_W / (alpha (x) beta) summed by BLAS this is a few ulp per term (tests: 1e-12
-// relative), the reference's own BLAS order being unspecified.
+// K3s, the fused walk: k_tile_walk over the W tiles that spread_build.hip writes, in the
+// line format of tile_lines.h (the algorithm is described there). This file holds the walk
+// and nothing else -- profiles/pmc_traffic.json keys the walk's traffic record on this
+// file's sha256, so an edit here means "the walk changed". spread_ref.hip includes it for
+// the F-writing instantiation (MODE_F), which only the test-reference library launches.
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "common.h"
-
-// LG_REFERENCE_PATHS (test-reference build, lib/liblgcnhs_ref.so, include/lgcnhs_ref.h): the
-// per-tile build passes, the F-writing walk and the two-kernel top-K merge, kept as bitwise
-// references for the product's group build and fused walk. The product library
-// (lib/liblgcnhs.so) is built without them.
-#ifndef LG_REFERENCE_PATHS
-#define LG_REFERENCE_PATHS 0
-#endif
-#if LG_REFERENCE_PATHS
-#include "lgcnhs_ref.h"
-#endif
+#include "score_stream.h"
+#include "tile_lines.h"
 
 namespace lg {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// A W tile is one 128-byte LINE per item row i at lines[i * 32 ..] (32 words) plus, for rows
-// that do not fit, a run of 16-byte units in an overflow array. Word 0 of the line is the
-// header: bit 31 = V format, bit 30 = overflow, bit 29 = slow (a V row, or a P row with a
-// degree class >= kInvTab: the walk's general decode), bits 0-28 = the overflow run's first
-// unit (ovf[u].x = the number of data units that follow it). No per-row metadata: the walk
-// reads the line of every item of its user straight from i * 128. Line I (one past the last
-// item) is all zero: the walk's padding rows read it.
-//
-// P rows (<= the hub threshold's pairs, the common case): one 4-byte slot per (user v,
-//   item j) PAIR behind the row (v in users(i), j in items(v) inside the tile), in pair order
-//   (users ascending, each user's items ascending):
-//     bits 0-15  j - item_begin
-//     bits 16-30 the 1-based class of v's degree k_v (fl(1 / k_v) = inv[class]; classes
-//                < kInvTab are cached in LDS); bit 31 clear (it marks V entries); a zero
-//                word is padding
-//   line words 1..31 hold the first 31 slots, the overflow units 4 slots each.
-// V rows (hub items, more pairs than the threshold; merged while building): one 16-byte
-//   entry per distinct column, ascending: {0x80000000 | (j - item_begin), fp64
-//   general_W[i][j] (lo, hi), 0}; line units 1..7 hold the first 7, the overflow units one
-//   each.
-//   A V row with more than width / 2 + 8 entries (hub items held by a large share of the
-//   users: nearly every column) is DENSE instead: its line holds only the header, and its
-//   overflow run (header x = kRunDense | n, n = ceil(width / 2) data units) holds the row's
-//   general_W of columns 2q and 2q + 1 in unit q as two fp64 (zeros included) -- 8 bytes per
-//   column instead of 16 per entry, read with no column index (the walk's hub rows are bound
-//   by these reads). The sparse run's allocation (1 + min(pairs, width) - 7 units) covers it.
-// Neither format depends on lambda (ra / rb are applied by the walk), so a lambda sweep
-// reuses the built tiles.
-constexpr uint32_t kHdrV = 0x80000000u;
-constexpr uint32_t kHdrOvf = 0x40000000u;
-constexpr uint32_t kHdrSlow = 0x20000000u;
-constexpr uint32_t kHdrPtr = 0x1FFFFFFFu;
-constexpr uint32_t kEntV = 0x80000000u;
-constexpr uint32_t kRunDense = 0x80000000u;  // overflow run header: a dense V row
-constexpr int kLineSlots = 31;  // P slots in a line (word 0 is the header)
-constexpr int kLineEnts = 7;    // V entries in a line (unit 0 holds the header)
-constexpr int kInvTab = 512;    // degree classes whose fl(1/k) is cached in LDS
-
-__global__ __launch_bounds__(256) void k_inv_degree(const int64_t *__restrict__ rowptr,
-                                                    int64_t n, double *__restrict__ inv) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n) return;
-  inv[v] = 1.0 / (double)(rowptr[v + 1] - rowptr[v]);  // k_spread_general's fl(1/k_v)
-}
-
-#if LG_REFERENCE_PATHS
-__global__ __launch_bounds__(256) void k_tile_cursor(const int64_t *__restrict__ user_rowptr,
-                                                     const int32_t *__restrict__ user_items,
-                                                     int64_t n_users, int32_t item_end,
-                                                     const int64_t *__restrict__ cur,
-                                                     int64_t *__restrict__ end,
-                                                     uint16_t *__restrict__ count) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n_users) return;
-  const int64_t p0 = cur[v];
-  int64_t p = p0;
-  const int64_t pe = user_rowptr[v + 1];
-  while (p < pe && user_items[p] < item_end) ++p;
-  end[v] = p;
-  count[v] = (uint16_t)(p - p0);  // <= tile <= 8192
-}
-
-#endif  // LG_REFERENCE_PATHS
-// cur[v] = first position of user v's item row with item >= item_begin: the cursor state
-// of a tile walk that starts at item_begin instead of 0 (an item-range shard).
-__global__ __launch_bounds__(256) void k_tile_seek(const int64_t *__restrict__ user_rowptr,
-                                                   const int32_t *__restrict__ user_items,
-                                                   int64_t n_users, int32_t item_begin,
-                                                   int64_t *__restrict__ cur) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n_users) return;
-  cur[v] = lower_bound_i32(user_items, user_rowptr[v], user_rowptr[v + 1], item_begin);
-}
-
-#if LG_REFERENCE_PATHS
-// one wave per item row
-__global__ __launch_bounds__(256) void k_tile_bound(const int64_t *__restrict__ item_rowptr,
-                                                    const int32_t *__restrict__ item_users,
-                                                    int64_t n_items,
-                                                    const uint16_t *__restrict__ count,
-                                                    int64_t *__restrict__ bound) {
-  const int64_t i = (int64_t)blockIdx.x * 4 + threadIdx.x / 64;
-  if (i >= n_items) return;
-  const int lane = lane_id();
-  int64_t s = 0;
-  for (int64_t e = item_rowptr[i] + lane; e < item_rowptr[i + 1]; e += 64)
-    s += count[item_users[e]];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (lane == 0) bound[i] = s;
-}
-
-#endif  // LG_REFERENCE_PATHS
-// ra[i] = 1 / k_item[i]^(1 - lambda), rb[i] = 1 / k_item[i]^lambda (the same pow() calls as
-// k_hybrid_weight); a zero factor -> 1 (its rows / columns hold no paths).
-__global__ __launch_bounds__(256) void k_hybrid_recip(const double *__restrict__ k_item,
-                                                      int64_t n, double lambda,
-                                                      double *__restrict__ ra,
-                                                      double *__restrict__ rb) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double a = pow(k_item[i], 1.0 - lambda), b = pow(k_item[i], lambda);
-  ra[i] = a != 0.0 ? 1.0 / a : 1.0;
-  rb[i] = b != 0.0 ? 1.0 / b : 1.0;
-}
-
-// ------------------------------------------------------------------- the rows pass
-// Slot p of a row: line word 1 + p for p < 31, else word (p - 31) of the overflow run's
-// data units (the run's unit 0 is its header).
-__device__ __forceinline__ void put_slot(uint32_t *__restrict__ line, uint32_t *__restrict__ ovf,
-                                         int64_t ou, int64_t p, uint32_t w) {
-  if (p < kLineSlots) line[1 + p] = w;
-  else ovf[(ou + 1) * 4 + (p - kLineSlots)] = w;
-}
-
-// The dense form of a V row from its accumulator acc[0 .. width) (threads t = t0 .. of a
-// stride-ts group write): the line's header and zero words, the run header, the data units.
-__device__ __forceinline__ bool hub_row_dense(int nz, int width) { return nz > width / 2 + 8; }
-__device__ void write_hub_row_dense(const double *acc, int width, uint32_t *line, uint32_t *ov,
-                                    int64_t ou, int t0, int ts) {
-  const int nd = (width + 1) / 2;
-  for (int t = t0; t < 32; t += ts) line[t] = t == 0 ? (kHdrV | kHdrSlow | kHdrOvf | (uint32_t)ou) : 0u;
-  for (int t = t0; t < 4; t += ts) ov[ou * 4 + t] = t == 0 ? (kRunDense | (uint32_t)nd) : 0u;
-  for (int q = t0; q < nd; q += ts) {
-    const uint64_t a = (uint64_t)__double_as_longlong(acc[2 * q]);
-    const uint64_t b = 2 * q + 1 < width ? (uint64_t)__double_as_longlong(acc[2 * q + 1]) : 0ull;
-    *reinterpret_cast<uint4 *>(ov + 4 * (ou + 1 + q)) =
-        uint4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-  }
-}
-
-#if LG_REFERENCE_PATHS
-// P rows: one wave per item row with bound[i] <= vthr pairs. Every word of the line and of
-// the overflow run is written exactly once (header, pairs, zero padding), so no stale data
-// of an earlier tile survives and no two stores of the wave hit one word.
-__global__ __launch_bounds__(256) void k_tile_rows(
-    const int64_t *__restrict__ item_rowptr, const int32_t *__restrict__ item_users,
-    const int32_t *__restrict__ user_items, const uint16_t *__restrict__ user_cls,
-    int64_t n_items, const int64_t *__restrict__ cur, const uint16_t *__restrict__ count,
-    int32_t item_begin, const int64_t *__restrict__ bound, int64_t vthr,
-    const int64_t *__restrict__ ovf_ptr, uint32_t *__restrict__ lines,
-    uint32_t *__restrict__ ovf, int32_t *__restrict__ row_len) {
-  const int64_t i = (int64_t)blockIdx.x * 4 + threadIdx.x / 64;
-  if (i >= n_items) return;
-  const int lane = lane_id();
-  const int64_t nb = bound[i];
-  if (nb > vthr) return;  // hub row: k_tile_rows_hub
-  uint32_t *line = lines + i * 32;
-  const bool has_ovf = nb > kLineSlots;
-  const int64_t ou = has_ovf ? ovf_ptr[i] : 0;
-  const int64_t n_units = has_ovf ? (nb - kLineSlots + 3) / 4 : 0;
-  const int64_t cap = kLineSlots + 4 * n_units;
-  if (has_ovf && lane < 4) ovf[ou * 4 + lane] = lane == 0 ? (uint32_t)n_units : 0u;
-  for (int64_t p = nb + lane; p < cap; p += 64) put_slot(line, ovf, ou, p, 0u);
-  // the pairs: users of i ascending, each user's items in the tile ascending
-  int64_t n = 0;
-  bool far = false;
-  const int64_t e1 = item_rowptr[i + 1];
-  for (int64_t e0 = item_rowptr[i]; e0 < e1; e0 += 64) {
-    const int64_t e = e0 + lane;
-    int32_t v = 0;
-    int c = 0;
-    if (e < e1) {
-      v = item_users[e];
-      c = count[v];
-    }
-    int pre = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(pre, o);
-      if (lane >= o) pre += y;
-    }
-    const int total = __shfl(pre, 63);
-    pre -= c;
-    if (c) {
-      const int64_t s0 = cur[v];
-      const uint32_t cl = (uint32_t)user_cls[v];
-      far |= cl >= (uint32_t)kInvTab;
-      for (int q = 0; q < c; ++q)
-        put_slot(line, ovf, ou, n + pre + q,
-                 (cl << 16) | (uint32_t)(user_items[s0 + q] - item_begin));
-    }
-    n += total;
-  }
-  const bool slow = __ballot(far) != 0;
-  if (lane == 0) {
-    line[0] = (has_ovf ? (kHdrOvf | (uint32_t)ou) : 0u) | (slow ? kHdrSlow : 0u);
-    if (row_len) row_len[i] = (int32_t)nb;
-  }
-}
-
-// V rows (bound > vthr pairs, hub items): one 256-thread block per row (grid-stride over the
-// hub list), the tile as a dense LDS accumulator of general_W, users walked in ascending
-// order as in k_spread_general, then the touched columns written as ascending entries.
-__global__ __launch_bounds__(256) void k_tile_rows_hub(
-    const int64_t *__restrict__ hub_rows, const int64_t *__restrict__ n_hub,
-    const int64_t *__restrict__ item_rowptr, const int32_t *__restrict__ item_users,
-    const int32_t *__restrict__ user_items, const double *__restrict__ inv_deg,
-    const int64_t *__restrict__ cur, const uint16_t *__restrict__ count, int32_t item_begin,
-    int32_t tile, const int64_t *__restrict__ ovf_ptr, uint32_t *__restrict__ lines,
-    uint32_t *__restrict__ ovf, int32_t *__restrict__ row_len) {
-  extern __shared__ double acc[];  // tile doubles
-  __shared__ int wsum[4];
-  const int64_t nh = *n_hub;
-  for (int64_t h = blockIdx.x; h < nh; h += gridDim.x) {
-    const int64_t i = hub_rows[h];
-    for (int j = threadIdx.x; j < tile; j += blockDim.x) acc[j] = 0.0;
-    __syncthreads();
-    for (int64_t e = item_rowptr[i]; e < item_rowptr[i + 1]; ++e) {
-      const int32_t v = item_users[e];
-      const int c = count[v];
-      if (c == 0) continue;  // uniform across the block: no barrier skipped unevenly
-      const double wv = inv_deg[v];
-      const int64_t s0 = cur[v];
-      for (int q = threadIdx.x; q < c; q += blockDim.x) acc[user_items[s0 + q] - item_begin] += wv;
-      __syncthreads();  // the next user may hit the same columns from other threads
-    }
-    uint32_t *line = lines + i * 32;
-    const int64_t ou = ovf_ptr[i];
-    if (threadIdx.x == 0) wsum[0] = 0;
-    __syncthreads();
-    {
-      int c = 0;
-      for (int j = threadIdx.x; j < tile; j += blockDim.x) c += acc[j] != 0.0;
-      atomicAdd(&wsum[0], c);
-    }
-    __syncthreads();
-    const int nzr = wsum[0];
-    __syncthreads();
-    if (hub_row_dense(nzr, tile)) {  // (tile = this tile's width here)
-      write_hub_row_dense(acc, tile, line, ovf, ou, threadIdx.x, blockDim.x);
-      if (threadIdx.x == 0 && row_len) row_len[i] = nzr;
-      __syncthreads();
-      continue;
-    }
-    int base = 0;
-    for (int j0 = 0; j0 < tile; j0 += blockDim.x) {
-      const int j = j0 + threadIdx.x;
-      const bool nz = j < tile && acc[j] != 0.0;
-      const uint64_t b = __ballot(nz);
-      const int w = threadIdx.x / 64;
-      if (lane_id() == 0) wsum[w] = __popcll(b);
-      __syncthreads();
-      int before_w = 0, total = 0;
-      for (int q = 0; q < 4; ++q) {
-        if (q < w) before_w += wsum[q];
-        total += wsum[q];
-      }
-      if (nz) {
-        const uint64_t bits = (uint64_t)__double_as_longlong(acc[j]);
-        const int64_t e = base + before_w + __popcll(b & lanemask_lt());
-        uint32_t *u4 = e < kLineEnts ? line + 4 * (1 + e) : ovf + 4 * (ou + 1 + (e - kLineEnts));
-        *reinterpret_cast<uint4 *>(u4) =
-            uint4{kEntV | (uint32_t)j, (uint32_t)bits, (uint32_t)(bits >> 32), 0u};
-      }
-      base += total;
-      __syncthreads();
-    }
-    // header, the unused line units, the overflow run's header
-    const bool has_ovf = base > kLineEnts;
-    if (threadIdx.x < 32) {
-      const int t = threadIdx.x;  // line word t
-      const int unit = t / 4;
-      if (t == 0) line[0] = kHdrV | kHdrSlow | (has_ovf ? (kHdrOvf | (uint32_t)ou) : 0u);
-      else if (unit == 0 || unit > base) line[t] = 0u;
-    }
-    if (has_ovf && threadIdx.x < 4)
-      ovf[ou * 4 + threadIdx.x] = threadIdx.x == 0 ? (uint32_t)(base - kLineEnts) : 0u;
-    if (threadIdx.x == 0 && row_len) row_len[i] = base;
-    __syncthreads();
-  }
-}
-
-#endif  // LG_REFERENCE_PATHS
-
-__global__ __launch_bounds__(256) void k_hub_list(const int64_t *__restrict__ bound,
-                                                  int64_t n_items, int64_t vthr,
-                                                  unsigned long long *__restrict__ n_hub,
-                                                  int64_t *__restrict__ hub_rows) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_items) return;
-  if (bound[i] > vthr) hub_rows[atomicAdd(n_hub, 1ull)] = i;
-}
-
-// ------------------------------------------------------------ group build (S tiles at once)
-// The per-tile passes above visit every (item row, user) pair once per TILE, although at C5
-// a user has ~0.2 items in a 2048-column tile: 489 tiles x 1e8 visits of gathered counts.
-// The group passes visit each pair once per GROUP of up to kGroupMax consecutive tiles and
-// write the group's tiles together (tile t of the group at lines + t (n_items + 1) 32 words,
-// its overflow runs at ovf + 4 ovf_base[t] words). Every word equals the per-tile build's
-// (same slot order, same headers; the caller places the runs with the same exclusive prefix).
-constexpr int kGroupMax = 16;
-constexpr int kGroupWide = 8;  // groups of tiles wider than 4096 columns (13-bit item codes)
-
-// counts[v][t] (kGroupMax uint16 per user: two 16-byte halves, tiles 0-7 and 8-15) = the
-// items of user v in tile t of the group ([group_begin + t tile, min(group_begin + (t + 1)
-// tile, stop))), end[v] = the position after the group's last; cur[v] = the first position
-// with item >= group_begin.
-// rec[v] (16 bytes, what k_group_rows gathers per (item, user) pair instead of counts, cur,
-// the class and the items): x = n (the user's items in the group, saturated at 255) |
-// class << 8; for n <= kRecItems the items as 16-bit codes t << cs | (item - tile t's first
-// item) in y, z, w (low half first; cs = code_shift(n_tiles): 13 for groups of <= 8 tiles,
-// 12 for more, whose tiles are <= 4096 wide); else y = cur[v] (the rows read user_items).
-constexpr int kRecItems = 6;
-__host__ __device__ constexpr int code_shift(int n_tiles) { return n_tiles <= kGroupWide ? 13 : 12; }
-__global__ __launch_bounds__(256) void k_group_cursor(const int64_t *__restrict__ user_rowptr,
-                                                      const int32_t *__restrict__ user_items,
-                                                      const uint16_t *__restrict__ user_cls,
-                                                      int64_t n_users, int32_t group_begin,
-                                                      int32_t tile, int32_t n_tiles,
-                                                      int32_t stop, const int64_t *__restrict__ cur,
-                                                      int64_t *__restrict__ end,
-                                                      uint4 *__restrict__ counts,
-                                                      uint4 *__restrict__ rec) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n_users) return;
-  const int cs = code_shift(n_tiles);
-  const int64_t p0 = cur[v];
-  int64_t p = p0;
-  const int64_t pe = user_rowptr[v + 1];
-  // the group's items: [group_begin, glim); an item's tile by one division (a user has few
-  // items in a group: ~1.6 at C5)
-  const int64_t gl = (int64_t)group_begin + (int64_t)n_tiles * tile;
-  const int32_t glim = (int32_t)(gl < stop ? gl : stop);
-  uint32_t c8[kGroupMax / 2];  // per-tile counts, two tiles per word (16-bit fields)
-#pragma unroll
-  for (int h = 0; h < kGroupMax / 2; ++h) c8[h] = 0;
-  uint32_t code[kRecItems];
-#pragma unroll
-  for (int k = 0; k < kRecItems; ++k) code[k] = 0;
-  int n = 0;
-  for (int32_t it = p < pe ? user_items[p] : 0x7fffffff; it < glim;
-       it = p < pe ? user_items[p] : 0x7fffffff) {
-    const uint32_t rel = (uint32_t)(it - group_begin);  // (cur: it >= group_begin)
-    const uint32_t t = rel / (uint32_t)tile;
-    const uint32_t cd = t << cs | (rel - t * (uint32_t)tile);
-#pragma unroll
-    for (int k = 0; k < kRecItems; ++k)
-      if (n == k) code[k] = cd;
-    const uint32_t inc = 1u << (16 * (t & 1));
-#pragma unroll
-    for (int h = 0; h < kGroupMax / 2; ++h) c8[h] += t >> 1 == (uint32_t)h ? inc : 0u;
-    ++n;
-    ++p;
-  }
-  end[v] = p;  // (the counts of a tile are <= tile <= 8192: no carry between the fields)
-  counts[2 * v] = uint4{c8[0], c8[1], c8[2], c8[3]};
-  counts[2 * v + 1] = uint4{c8[4], c8[5], c8[6], c8[7]};
-  const uint32_t hx = (uint32_t)(n < 255 ? n : 255) | (uint32_t)user_cls[v] << 8;
-  rec[v] = n <= kRecItems
-               ? uint4{hx, code[0] | code[1] << 16, code[2] | code[3] << 16, code[4] | code[5] << 16}
-               : uint4{hx, (uint32_t)p0, 0u, 0u};
-}
-
-// tile t's count in a user's 8-tile half c (t < 8)
-__device__ __forceinline__ uint32_t count_of(const uint4 &c, int t) {
-  const uint32_t w = t < 2 ? c.x : (t < 4 ? c.y : (t < 6 ? c.z : c.w));
-  return (t & 1) ? w >> 16 : w & 0xFFFFu;
-}
-// tile t's count (t < 16) in a user's two halves
-__device__ __forceinline__ uint32_t count_of2(const uint4 &lo, const uint4 &hi, int t) {
-  return t < 8 ? count_of(lo, t) : count_of(hi, t - 8);
-}
-
-// bound[t][i] = sum over the users v of item i of counts[v][t] (the pairs behind row i in
-// tile t). 16 lanes per item row, 4 rows per wave (rows of ~100 users fill a 64-lane wave
-// poorly, and a wave's fixed costs -- row pointers, the reduction, the stores -- are then
-// shared by 4 rows). Per round each lane gathers the counts of 8 of its row's users (128 per
-// row; every load is issued, clamped to a valid index, before any is used: one wait for the
-// ids, one for the counts; the second 8-tile half only for groups of more than 8), sums them
-// per tile in 32 bits (<= 8 x 8192), then into 64 bits. The 16 lanes' 16 per-tile sums are
-// reduced by halving exchanges: over xor 8, 4, 2, 1 each lane keeps half of its tiles and
-// adds its partner's sums of those (16 -> 8 -> 4 -> 2 -> 1 tiles): lane t of the row ends
-// with tile t's total (15 shuffles instead of 16 x 4). At C5 the kernel is bound by the
-// random 16-byte count gathers (one per (row, user) pair and group), not by its arithmetic.
-static_assert(kGroupMax == 16, "k_group_bound's halving reduction is written for 16 tiles");
-__global__ __launch_bounds__(256) void k_group_bound(const int64_t *__restrict__ item_rowptr,
-                                                     const int32_t *__restrict__ item_users,
-                                                     int64_t n_items,
-                                                     const uint4 *__restrict__ counts,
-                                                     int32_t n_tiles, int64_t *__restrict__ bound) {
-  constexpr int kU = 8;  // users per lane per round
-  const int lane = lane_id(), sub = lane & 15;
-  const int64_t i = ((int64_t)blockIdx.x * 4 + threadIdx.x / 64) * 4 + (lane >> 4);
-  const bool live = i < n_items;  // (no early exit: the reduction needs every lane)
-  const bool wide = n_tiles > 8;  // (uniform)
-  const int64_t b = live ? item_rowptr[i] : 0, e1 = live ? item_rowptr[i + 1] : 0;
-  uint64_t s[kGroupMax];
-#pragma unroll
-  for (int t = 0; t < kGroupMax; ++t) s[t] = 0;
-  // (a round runs only while some row of the wave has users left: there are interactions,
-  // so index 0 of item_users and of counts is valid for the clamped lanes)
-  for (int64_t r0 = b; __ballot(r0 < e1) != 0; r0 += 16 * kU) {
-    int32_t v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int64_t e = r0 + sub + 16 * u;
-      v[u] = item_users[e < e1 ? e : 0];
-    }
-    uint4 cl[kU], ch[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      cl[u] = counts[2 * (int64_t)v[u]];
-      ch[u] = wide ? counts[2 * (int64_t)v[u] + 1] : uint4{0u, 0u, 0u, 0u};
-    }
-    uint32_t rs[kGroupMax];
-#pragma unroll
-    for (int t = 0; t < kGroupMax; ++t) rs[t] = 0;
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const bool in = r0 + sub + 16 * u < e1;
-      const uint4 zl = in ? cl[u] : uint4{0u, 0u, 0u, 0u};
-      const uint4 zh = in ? ch[u] : uint4{0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int t = 0; t < kGroupMax; ++t) rs[t] += count_of2(zl, zh, t);
-    }
-#pragma unroll
-    for (int t = 0; t < kGroupMax; ++t) s[t] += rs[t];
-  }
-  // halving exchanges within the row's 16 lanes: after the step over xor m the lane keeps
-  // the tiles whose bit (m) equals its own
-  uint64_t r8[8], r4[4], r2[2];
-  const bool h3 = sub & 8, h2 = sub & 4, h1 = sub & 2, h0 = sub & 1;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    r8[j] = (h3 ? s[j + 8] : s[j]) + __shfl_xor(h3 ? s[j] : s[j + 8], 8);  // tiles 8 h3 + j
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    r4[j] = (h2 ? r8[j + 4] : r8[j]) + __shfl_xor(h2 ? r8[j] : r8[j + 4], 4);  // + 4 h2 + j
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-    r2[j] = (h1 ? r4[j + 2] : r4[j]) + __shfl_xor(h1 ? r4[j] : r4[j + 2], 2);  // + 2 h1 + j
-  const uint64_t r1 = (h0 ? r2[1] : r2[0]) + __shfl_xor(h0 ? r2[0] : r2[1], 1);  // + h0
-  if (live && sub < n_tiles) bound[(int64_t)sub * n_items + i] = (int64_t)r1;
-}
-
-// Overflow units (run header + data) of a row with nb pairs in a tile of width w: P rows
-// (nb <= vthr) 1 + ceil((nb - 31) / 4) past the line's 31 slots, V rows (hub items)
-// 1 + (min(nb, w) - 7) past the line's 7 entries, else 0 (= ops._run_units).
-__device__ __forceinline__ int64_t run_units(int64_t nb, int64_t vthr, int64_t w) {
-  if (nb > vthr) {
-    const int64_t len = nb < w ? nb : w;
-    return len > kLineEnts ? 1 + (len - kLineEnts) : 0;
-  }
-  return nb > kLineSlots ? 1 + (nb - kLineSlots + 3) / 4 : 0;
-}
-
-__device__ __forceinline__ int64_t tile_width(int32_t group_begin, int32_t tile, int t,
-                                              int32_t stop) {
-  const int64_t b = (int64_t)group_begin + (int64_t)t * tile;
-  const int64_t e = b + tile < stop ? b + tile : stop;
-  return e - b;
-}
-
-// units[t][i] = run_units of row i in tile t (the caller's inclusive scan over the flat
-// [n_tiles][n_items] array places the runs: tile by tile, rows ascending)
-__global__ __launch_bounds__(256) void k_group_units(const int64_t *__restrict__ bound,
-                                                     int64_t n_items, int32_t group_begin,
-                                                     int32_t tile, int32_t n_tiles, int32_t stop,
-                                                     int64_t vthr, int64_t *__restrict__ units) {
-  const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= n_items * n_tiles) return;
-  const int t = (int)(x / n_items);
-  units[x] = run_units(bound[x], vthr, tile_width(group_begin, tile, t, stop));
-}
-
-// Inclusive prefix sum over the wave's 64 lanes by DPP (no LDS round trips): row_shr 1, 2,
-// 4, 8 inside each 16-lane row, then row_bcast 15 / 31 add the earlier rows' totals.
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);  // row_shr:2
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);  // row_shr:4
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);  // row_shr:8
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);  // row_bcast:15
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31
-  return x;
-}
-
-// lane t's 64-bit value as a wave-uniform scalar
-__device__ __forceinline__ int64_t readlane64(int64_t x, int t) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, t);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)x >> 32), t);
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// P rows of every tile of the group: one wave per item row (tiles whose row is a hub row,
-// bound > vthr, are left to k_group_rows_hub). The row's lines (kGroupMax x 128 bytes) are
-// assembled in the wave's LDS and written with two coalesced 16-byte-per-lane stores at the
-// end (the slots of a line come from ~20 lanes over several chunks: written straight to
-// global memory they took ~5 sparse store instructions per (row, tile)); slots past a line's
-// 31 go to the overflow run directly. Per chunk of 64 users (lane = user, ascending): the
-// user's per-tile item counts (from its record's item codes, or its counts for users with
-// more than kRecItems items in the group), two tiles per word as 16-bit fields (a P row's
-// prefix never exceeds its bound <= vthr < 2^16; hub tiles' counts are masked to 0), one
-// DPP prefix sum per word; then per tile t the lane's first slot position minus its item
-// index in the group, D_t (an LDS table, [t][lane]), so each of the lane's items k lands
-// at slot D_t + k with one table read -- one pass over the user's items instead of one per
-// tile. A chunk's user records are gathered one chunk ahead and its users two ahead
-// (unconditional loads, clamped into the row).
-__global__ __launch_bounds__(256) void k_group_rows(
-    const int64_t *__restrict__ item_rowptr, const int32_t *__restrict__ item_users,
-    const int32_t *__restrict__ user_items, int64_t n_items, const uint4 *__restrict__ counts,
-    const uint4 *__restrict__ rec, int32_t group_begin, int32_t tile, int32_t n_tiles,
-    int32_t stop, const int64_t *__restrict__ bound, int64_t vthr,
-    const int64_t *__restrict__ units_incl,
-    uint32_t *__restrict__ lines, uint32_t *__restrict__ ovf, int32_t *__restrict__ row_len) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_line[4][kGroupMax * 32];
-  __shared__ uint32_t s_pos[4][kGroupMax][64];
-  __shared__ uint32_t s_ovw[4][kGroupMax];  // tile t's run: its first data word in ovf
-  const int wv = threadIdx.x / 64;
-  const int64_t i = (int64_t)blockIdx.x * 4 + wv;
-  if (i >= n_items) return;  // (whole waves: the LDS is per wave, no block barrier)
-  const int lane = lane_id();
-  // lane t < n_tiles: row i's pairs, run offset (relative to the tile's runs) and the
-  // tile's first unit in ovf
-  int64_t nbl = 0, oul = 0, obl = 0;
-  if (lane < n_tiles) {
-    const int64_t x = (int64_t)lane * n_items + i;
-    nbl = bound[x];
-    obl = lane ? units_incl[(int64_t)lane * n_items - 1] : 0;
-    oul = units_incl[x] - run_units(nbl, vthr, tile_width(group_begin, tile, lane, stop)) - obl;
-  }
-  const int64_t eb = item_rowptr[i], e1 = item_rowptr[i + 1];
-  const int cs = code_shift(n_tiles);
-  const uint32_t cmask = (1u << cs) - 1u;
-  const bool wide = n_tiles > 8;  // (uniform)
-  uint32_t *line_s = s_line[wv];
-  {  // the lines start all zero (padding); 2 x 16 bytes per lane
-    uint4 *l4 = reinterpret_cast<uint4 *>(line_s);
-    l4[lane] = uint4{0u, 0u, 0u, 0u};
-    l4[64 + lane] = uint4{0u, 0u, 0u, 0u};
-  }
-  wave_sync();
-  const bool has_run_l = lane < n_tiles && nbl <= vthr && nbl > kLineSlots;
-  if (lane < n_tiles) s_ovw[wv][lane] = (uint32_t)((obl + oul + 1) * 4);
-  uint32_t pmask = 0;  // P tiles of this row (uniform)
-#pragma unroll
-  for (int t = 0; t < kGroupMax; ++t)
-    if (t < n_tiles && readlane64(nbl, t) <= vthr) pmask |= 1u << t;
-  // overflow runs of the P tiles: header unit and the padding past the row's pairs
-  uint32_t runs = (uint32_t)__ballot(has_run_l);
-  while (runs) {
-    const int t = __builtin_ctz(runs);
-    runs &= runs - 1;
-    const int64_t nb = readlane64(nbl, t);
-    const int64_t ob = readlane64(obl, t) + readlane64(oul, t);  // the run's header unit
-    const int64_t n_units = (nb - kLineSlots + 3) / 4;
-    if (lane < 4) ovf[ob * 4 + lane] = lane == 0 ? (uint32_t)n_units : 0u;
-    for (int64_t p = nb + lane; p < kLineSlots + 4 * n_units; p += 64)
-      ovf[(ob + 1) * 4 + (p - kLineSlots)] = 0u;
-  }
-  uint32_t m8[kGroupMax / 2];
-#pragma unroll
-  for (int h = 0; h < kGroupMax / 2; ++h) {
-    const uint32_t lo = ((pmask >> (2 * h)) & 1) ? 0xFFFFu : 0u;
-    const uint32_t hi = ((pmask >> (2 * h + 1)) & 1) ? 0xFFFF0000u : 0u;
-    m8[h] = lo | hi;
-  }
-  uint32_t n[kGroupMax];  // pairs written so far per tile (uniform)
-#pragma unroll
-  for (int t = 0; t < kGroupMax; ++t) n[t] = 0;
-  uint32_t farbits = 0;
-  auto user_at = [&](int64_t e0) __attribute__((always_inline)) {
-    const int64_t e = e0 + lane;
-    return item_users[e < e1 ? e : e1 - 1];
-  };
-  int32_t v_c = 0, v_n = 0;
-  uint4 r_c{0u, 0u, 0u, 0u};
-  if (eb < e1) {
-    v_c = user_at(eb);
-    v_n = user_at(eb + 64);
-    r_c = rec[v_c];
-  }
-  for (int64_t e0 = eb; e0 < e1; e0 += 64) {
-    const int32_t v = v_c;
-    const uint4 rc = e0 + lane < e1 ? r_c : uint4{0u, 0u, 0u, 0u};
-    const uint32_t nu = rc.x & 0xFFu;  // the user's items in the group (saturated)
-    const bool longu = nu > (uint32_t)kRecItems;
-    uint32_t c8[kGroupMax / 2];  // the user's per-tile counts, two tiles per word
-#pragma unroll
-    for (int h = 0; h < kGroupMax / 2; ++h) c8[h] = 0;
-    // (the rare users with more items than the record holds load their counts before the
-    // prefetch below is issued: waiting for these loads then drains nothing younger)
-    if (longu) {
-      const uint4 lo = counts[2 * (int64_t)v];
-      const uint4 hi = wide ? counts[2 * (int64_t)v + 1] : uint4{0u, 0u, 0u, 0u};
-      c8[0] = lo.x, c8[1] = lo.y, c8[2] = lo.z, c8[3] = lo.w;
-      c8[4] = hi.x, c8[5] = hi.y, c8[6] = hi.z, c8[7] = hi.w;
-    }
-    v_c = v_n;
-    r_c = rec[v_n];           // the next chunk's records
-    v_n = user_at(e0 + 128);  // the users of the one after
-    if (!longu) {  // per-tile counts from the item codes
-#pragma unroll
-      for (int k = 0; k < kRecItems; ++k) {
-        const uint32_t wd = k < 2 ? rc.y : (k < 4 ? rc.z : rc.w);
-        const uint32_t cd = (k & 1) ? wd >> 16 : wd & 0xFFFFu;
-        if ((uint32_t)k < nu) {
-          const uint32_t t = cd >> cs;
-          const uint32_t inc = 1u << (16 * (t & 1));
-#pragma unroll
-          for (int h = 0; h < kGroupMax / 2; ++h) c8[h] += t >> 1 == (uint32_t)h ? inc : 0u;
-        }
-      }
-    }
-    uint32_t any = 0;
-#pragma unroll
-    for (int h = 0; h < kGroupMax / 2; ++h) any |= c8[h] & m8[h];
-    if (__ballot(any != 0) == 0) continue;  // no pair in any P tile
-    // D_t per tile: (pairs before this chunk) + (this chunk's lanes before this one) - (the
-    // user's items in tiles < t)
-    uint32_t off = 0, ntot = 0;
-#pragma unroll
-    for (int h = 0; h < kGroupMax / 2; ++h) {
-      if (2 * h >= n_tiles) break;
-      const uint32_t wm = c8[h] & m8[h];
-      uint32_t pre = wm;
-      if (__ballot(pre != 0) != 0) pre = wave_incl_sum(pre);
-      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)pre, 63);
-      pre -= wm;
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int t = 2 * h + b;
-        const uint32_t pb = (pre >> (16 * b)) & 0xFFFFu;
-        s_pos[wv][t][lane] = n[t] + pb - off;
-        n[t] += (total >> (16 * b)) & 0xFFFFu;
-        off += (c8[h] >> (16 * b)) & 0xFFFFu;
-      }
-    }
-    ntot = off;  // the user's items in the group's tiles (all of them, n_tiles <= 16)
-    wave_sync();
-    const int64_t s0 = longu ? (int64_t)rc.y : 0;
-    const uint32_t cl = rc.x >> 8;
-    uint32_t tl = 0;  // (long users: the tile of the current item, items ascending)
-    for (uint32_t k = 0; k < ntot; ++k) {
-      uint32_t t, col;
-      if (!longu) {
-        const uint32_t wd = k < 2 ? rc.y : (k < 4 ? rc.z : rc.w);
-        const uint32_t cd = (k & 1) ? wd >> 16 : wd & 0xFFFFu;
-        t = cd >> cs;
-        col = cd & cmask;
-      } else {
-        const uint32_t rel = (uint32_t)(user_items[s0 + k] - group_begin);
-        while (rel >= (tl + 1) * (uint32_t)tile) ++tl;
-        t = tl;
-        col = rel - tl * (uint32_t)tile;
-      }
-      if ((pmask >> t) & 1u) {
-        const uint32_t pos = s_pos[wv][t][lane] + k;
-        const uint32_t word = (cl << 16) | col;
-        if (pos < (uint32_t)kLineSlots) line_s[t * 32 + 1 + pos] = word;
-        else ovf[(int64_t)s_ovw[wv][t] + (pos - kLineSlots)] = word;
-        if (cl >= (uint32_t)kInvTab) farbits |= 1u << t;
-      }
-    }
-  }
-  // headers (lane t: tile t) and row lengths, then the lines
-  uint32_t slowm = 0;
-#pragma unroll
-  for (int t = 0; t < kGroupMax; ++t)
-    if ((pmask >> t) & 1u) slowm |= __ballot((farbits >> t) & 1u) != 0 ? 1u << t : 0u;
-  if (lane < kGroupMax && ((pmask >> lane) & 1u)) {
-    line_s[lane * 32] = (nbl > kLineSlots ? (kHdrOvf | (uint32_t)oul) : 0u) |
-                        (((slowm >> lane) & 1u) ? kHdrSlow : 0u);
-    if (row_len) row_len[(int64_t)lane * n_items + i] = (int32_t)nbl;
-  }
-  wave_sync();
-  const int64_t tstride = (n_items + 1) * 32;  // words per tile of lines
-#pragma unroll
-  for (int r = 0; r < kGroupMax / 8; ++r) {
-    const int t = 8 * r + (lane >> 3), u = lane & 7;
-    if ((pmask >> t) & 1u)
-      *reinterpret_cast<uint4 *>(lines + (int64_t)t * tstride + i * 32 + 4 * u) =
-          reinterpret_cast<const uint4 *>(line_s)[t * 8 + u];
-  }
-}
-
-__device__ __forceinline__ void lds_add(double *acc, uint32_t col, double v) {
-  __hip_atomic_fetch_add(&acc[col], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Hub rows of the group (flat index t * n_items + i of rows with bound > vthr, listed by
-// k_hub_list over the [n_tiles][n_items] bounds): the dense accumulation of k_tile_rows_hub --
-// general_W[i][j] = the sum over i's users v, ascending, of fl(1/k_v) for each of v's items j
-// in tile t (on tile t's cursor cur[v] + v's items in tiles < t) -- by ONE WAVE per row, on
-// its own LDS accumulator. A hub item has up to all the users; the per-user metadata (the
-// user id, its 32-byte count record, its cursor and fl(1/k_v)) of 64 users is loaded by the
-// wave's lanes at once, and their items (~1-3 per user and tile) up to 256 at a time, each
-// lane finding the user of its entries by a binary search over the users' running counts;
-// the adds then go out user by user in ascending order, each an LDS atomic over the lanes
-// holding that user's entries. A wave's LDS operations are performed in order, so every
-// column is summed in ascending user order -- k_tile_rows_hub's sums, bit for bit -- with no
-// block barrier per user (that kernel's 256-thread block waited at one per user, and walked
-// the users one dependent load chain at a time).
-__global__ __launch_bounds__(256) void k_group_rows_hub(
-    const int64_t *__restrict__ hub_rows, const int64_t *__restrict__ n_hub,
-    const int64_t *__restrict__ item_rowptr, const int32_t *__restrict__ item_users,
-    const int32_t *__restrict__ user_items, const double *__restrict__ inv_deg,
-    int64_t n_items, const int64_t *__restrict__ cur, const uint4 *__restrict__ counts,
-    int32_t group_begin, int32_t tile, int32_t stop, const int64_t *__restrict__ bound,
-    int64_t vthr, const int64_t *__restrict__ units_incl, uint32_t *__restrict__ lines,
-    uint32_t *__restrict__ ovf, int32_t *__restrict__ row_len) {
-  extern __shared__ double lds_acc[];  // tile doubles per wave
-  const int nwb = blockDim.x / 64, wave = threadIdx.x / 64, lane = lane_id();
-  double *acc = lds_acc + (size_t)wave * tile;
-  const int64_t nh = *n_hub;
-  for (int64_t h = (int64_t)blockIdx.x * nwb + wave; h < nh; h += (int64_t)gridDim.x * nwb) {
-    const int64_t flat = hub_rows[h];
-    const int t = (int)(flat / n_items);
-    const int64_t i = flat - (int64_t)t * n_items;
-    const int32_t item_begin = group_begin + t * tile;
-    for (int j = lane; j < tile; j += 64) acc[j] = 0.0;
-    wave_sync();
-    const int64_t eb = item_rowptr[i], ee = item_rowptr[i + 1];
-    for (int64_t e0 = eb; e0 < ee; e0 += 64) {
-      const int64_t e = e0 + lane;
-      int c = 0;
-      int64_t s0 = 0;
-      double wv = 0.0;
-      if (e < ee) {
-        const int32_t v = item_users[e];
-        const uint4 lo = counts[2 * (int64_t)v], hi = counts[2 * (int64_t)v + 1];
-        c = (int)count_of2(lo, hi, t);
-        s0 = cur[v];
-        for (int q = 0; q < t; ++q) s0 += count_of2(lo, hi, q);
-        wv = inv_deg[v];
-      }
-      int incl = c;  // inclusive running count of the users' items (lane order = user order)
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-      }
-      const int total = __shfl(incl, 63);
-      const int pos = incl - c;
-      uint64_t users = __ballot(c > 0);
-      if (total <= 256) {
-        // entry p = r * 64 + lane: the (p - pos_l)-th item of the user l with
-        // pos_l <= p < incl_l (the first lane whose running count passes p)
-        int col[4];
-        double wt[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int p = 64 * r + lane;
-          col[r] = 0;
-          wt[r] = 0.0;
-          if (64 * r >= total) continue;  // (uniform)
-          int lo = 0, hi = 63;
-#pragma unroll
-          for (int st = 0; st < 6; ++st) {  // first lane l with incl_l > p
-            const int mid = (lo + hi) >> 1;
-            if (__shfl(incl, mid) > p) hi = mid;
-            else lo = mid + 1;
-          }
-          const int64_t s0l = __shfl(s0, lo);
-          const int pl = __shfl(pos, lo);
-          const double wl = __shfl(wv, lo);
-          if (p < total) {
-            col[r] = user_items[s0l + (p - pl)] - item_begin;
-            wt[r] = wl;
-          }
-        }
-        while (users) {
-          const int l = __builtin_ctzll(users);
-          users &= users - 1;
-          const int pl = __builtin_amdgcn_readlane(pos, l);
-          const int ql = __builtin_amdgcn_readlane(incl, l);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (64 * r >= ql || 64 * r + 64 <= pl) continue;  // (uniform)
-            const int p = 64 * r + lane;
-            if (p >= pl && p < ql) lds_add(acc, (uint32_t)col[r], wt[r]);
-          }
-        }
-      } else {  // (a chunk of users with more than 256 items in the tile: user by user)
-        while (users) {
-          const int l = __builtin_ctzll(users);
-          users &= users - 1;
-          const int cl = __builtin_amdgcn_readlane(c, l);
-          const int64_t s0l = __shfl(s0, l);
-          const double wl = __shfl(wv, l);
-          for (int q = lane; q < cl; q += 64)
-            lds_add(acc, (uint32_t)(user_items[s0l + q] - item_begin), wl);
-        }
-      }
-    }
-    wave_sync();
-    uint32_t *line = lines + (int64_t)t * (n_items + 1) * 32 + i * 32;
-    const int64_t tbase = t ? units_incl[(int64_t)t * n_items - 1] : 0;
-    uint32_t *ov = ovf + tbase * 4;
-    const int width = (int)tile_width(group_begin, tile, t, stop);
-    const int64_t ou = units_incl[flat] - run_units(bound[flat], vthr, width) - tbase;
-    int nzr = 0;
-    for (int j0 = 0; j0 < tile; j0 += 64)
-      nzr += __popcll(__ballot(j0 + lane < tile && acc[j0 + lane] != 0.0));
-    if (hub_row_dense(nzr, width)) {
-      write_hub_row_dense(acc, width, line, ov, ou, lane, 64);
-      if (lane == 0 && row_len) row_len[flat] = nzr;
-      wave_sync();
-      continue;
-    }
-    int base = 0;
-    for (int j0 = 0; j0 < tile; j0 += 64) {
-      const int j = j0 + lane;
-      const double x = j < tile ? acc[j] : 0.0;
-      const bool nz = x != 0.0;
-      const uint64_t b = __ballot(nz);
-      if (nz) {
-        const uint64_t bits = (uint64_t)__double_as_longlong(x);
-        const int64_t en = base + __popcll(b & lanemask_lt());
-        uint32_t *u4 = en < kLineEnts ? line + 4 * (1 + en) : ov + 4 * (ou + 1 + (en - kLineEnts));
-        *reinterpret_cast<uint4 *>(u4) =
-            uint4{kEntV | (uint32_t)j, (uint32_t)bits, (uint32_t)(bits >> 32), 0u};
-      }
-      base += __popcll(b);
-    }
-    const bool has_ovf = base > kLineEnts;
-    if (lane < 32) {
-      const int tw = lane;  // line word
-      const int unit = tw / 4;
-      if (tw == 0) line[0] = kHdrV | kHdrSlow | (has_ovf ? (kHdrOvf | (uint32_t)ou) : 0u);
-      else if (unit == 0 || unit > base) line[tw] = 0u;
-    }
-    if (has_ovf && lane < 4) ov[ou * 4 + lane] = lane == 0 ? (uint32_t)(base - kLineEnts) : 0u;
-    if (lane == 0 && row_len) row_len[flat] = base;
-    wave_sync();
-  }
-}
-
-template <int Q>
-__device__ __forceinline__ void load_frag(const float *__restrict__ p, float (&v)[Q]) {
-  const float4 *p4 = reinterpret_cast<const float4 *>(p);
-#pragma unroll
-  for (int t = 0; t < Q / 4; ++t) {
-    const float4 q = p4[t];
-    v[4 * t + 0] = q.x;
-    v[4 * t + 1] = q.y;
-    v[4 * t + 2] = q.z;
-    v[4 * t + 3] = q.w;
-  }
-}
-
-#if LG_REFERENCE_PATHS
-// Merge the tile's columns of (G *) F into running per-user top-K lists (io_val/io_idx,
-// sorted, index -1 = empty). D = 0: no G factor. One wave = NG groups of 16 users (rows);
-// lane (ul, gq) holds user ul of each group and items 4gq..4gq+3 of each 16-item step.
-// S = the per-user list stride in LDS (entries): 40 for k <= 24 after a walk's first span
-// (30 KiB blocks: 8 waves per CU, VGPR-limited), else 64*M. (A 3-slot load ring under a
-// 3-waves-per-SIMD register budget spilled and ran 40 % slower.)
-template <int D, int NG, int M, bool VEC, int S>
-__global__ __launch_bounds__(128) void k_tile_topk(
-    const double *__restrict__ F, int64_t ldf, int64_t n_rows, int32_t item_begin,
-    int32_t n_cols, const float *__restrict__ eu, const float *__restrict__ ei,
-    const int64_t *__restrict__ ex_rowptr, const int32_t *__restrict__ ex_col, int drop,
-    int k, int first, double *__restrict__ io_val, int64_t *__restrict__ io_idx) {
-  static_assert(S >= 32 && S <= 64 * M, "list stride");
-  constexpr int Q = D > 0 ? D / 4 : 1;
-  __shared__ double cs[2][NG][16][S];
-  __shared__ int ci[2][NG][16][S];
-  __shared__ int exs[2][64];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);  // uniform: SGPR bases
-  const int lane = lane_id();
-  const int ul = lane & 15, gq = lane >> 4;
-  const int64_t ubase = ((int64_t)blockIdx.x * 2 + wave) * (16 * NG);
-  if (ubase >= n_rows) return;
-
-  float uf[NG][Q];
-  bool uvalid[NG];
-  int cnt[NG], chk[NG];
-  bool dirty[NG];  // the user's list gained an entry in this call (first call: always)
-  double thr[NG];
-  int64_t ex_pos[NG], ex_hi[NG];
-  const int lim_end = item_begin + n_cols;
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int64_t r = ubase + g * 16 + ul;
-    uvalid[g] = r < n_rows;
-    const int64_t rr = uvalid[g] ? r : n_rows - 1;
-    if (D > 0) load_frag<Q>(eu + rr * D + gq * Q, uf[g]);
-    ex_pos[g] = 0;
-    ex_hi[g] = 0;
-    if (drop && ex_rowptr && uvalid[g]) {
-      ex_pos[g] = ex_rowptr[r];
-      ex_hi[g] = ex_rowptr[r + 1];
-    }
-    cnt[g] = 0;
-    chk[g] = 0;
-    dirty[g] = first != 0;
-    thr[g] = uvalid[g] ? neg_inf<double>() : __builtin_huge_val();
-  }
-  // exclusion cursors: first excluded item >= item_begin, all groups' searches in lockstep
-  // so their loads overlap; ex_next caches the item under the cursor (INT_MAX = none left)
-  int32_t ex_next[NG];
-  {
-    int64_t lo[NG], hi[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      lo[g] = ex_pos[g];
-      hi[g] = ex_hi[g];
-    }
-    for (;;) {
-      bool busy = false;
-      int32_t x[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) x[g] = lo[g] < hi[g] ? ex_col[(lo[g] + hi[g]) >> 1] : 0;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        if (lo[g] < hi[g]) {
-          const int64_t mid = (lo[g] + hi[g]) >> 1;
-          if (x[g] < item_begin) lo[g] = mid + 1;
-          else hi[g] = mid;
-        }
-        busy |= lo[g] < hi[g];
-      }
-      if (!__ballot(busy)) break;
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      ex_pos[g] = lo[g];
-      ex_next[g] = lo[g] < ex_hi[g] ? ex_col[lo[g]] : 0x7fffffff;
-    }
-  }
-  // running lists -> LDS (already sorted and exclusion-checked): the wave's NG*16 lists are
-  // contiguous in io_*, so they are read in one pass with 8 loads per lane in flight
-  if (!first) {
-    const int64_t base = ubase * k;
-    const int64_t lim = (n_rows - ubase) * k;
-    const int total = NG * 16 * k;
-    for (int t0 = 0; t0 < total; t0 += 64 * 8) {
-      int64_t id[8];
-      double vv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int t = t0 + q * 64 + lane;
-        const bool in = t < total && t < lim;
-        id[q] = in ? io_idx[base + t] : -1;
-        vv[q] = in ? io_val[base + t] : neg_inf<double>();
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int t = t0 + q * 64 + lane;
-        if (t < total) {
-          const int uu = t / k, e = t - uu * k;
-          cs[wave][uu >> 4][uu & 15][e] = vv[q];
-          ci[wave][uu >> 4][uu & 15][e] = id[q] >= 0 ? (int)id[q] : -1;
-        }
-      }
-    }
-    wave_sync();
-    // valid entries form a prefix (lists are sorted, drops written as -1 at the end): the
-    // 4 lanes of a user count a quarter each
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int *is = &ci[wave][g][ul][0];
-      int nv = 0;
-      for (int e = gq; e < k; e += 4) nv += is[e] >= 0;
-      nv += __shfl_xor(nv, 16);
-      nv += __shfl_xor(nv, 32);
-      if (uvalid[g]) {
-        cnt[g] = nv;
-        chk[g] = nv;
-        thr[g] = nv == k ? cs[wave][g][ul][k - 1] : neg_inf<double>();
-      }
-    }
-  }
-  const uint64_t same_user = 0x0001000100010001ull << ul;
-
-  auto compact_user = [&](int g, int u, int lim) __attribute__((always_inline)) {
-    const int n = __shfl(cnt[g], u);
-    const int c0 = __shfl(chk[g], u);
-    int64_t pos = __shfl(ex_pos[g], u);
-    const int64_t hi = __shfl(ex_hi[g], u);
-    int32_t nx = __shfl(ex_next[g], u);
-    double *ks = &cs[wave][g][u][0];
-    int *is = &ci[wave][g][u][0];
-    if (n > c0 && nx < lim) {  // the cached next exclusion decides without a load
-      while (pos < hi) {  // excluded items in [previous limit, lim): drop their entries
-        const int64_t e = pos + lane;
-        const int32_t x = e < hi ? ex_col[e] : 0x7fffffff;
-        const int nin = __popcll(__ballot(x < lim));
-        if (nin < 64) nx = __shfl(x, nin & 63);
-        if (nin == 0) break;
-        exs[wave][lane] = x;
-        wave_sync();
-        for (int j = c0 + lane; j < n; j += 64) {
-          const int item = is[j];
-          int a = 0, b = nin;
-          while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (exs[wave][mid] < item) a = mid + 1;
-            else b = mid;
-          }
-          if (a < nin && exs[wave][a] == item) ks[j] = neg_inf<double>();
-        }
-        wave_sync();
-        pos += nin;
-        if (nin < 64) break;
-      }
-      if (pos >= hi) nx = 0x7fffffff;
-    }
-    double t;
-    int tid;
-    const int nc = wave_compact<double, M>(ks, is, n, k, t, tid);
-    if (ul == u) {
-      cnt[g] = nc;
-      chk[g] = nc;
-      ex_pos[g] = pos;
-      ex_next[g] = nx;
-      thr[g] = !uvalid[g] ? __builtin_huge_val() : t;
-    }
-  };
-
-  // One 16-column step: the item fragment and the F values (clamped to valid memory, so
-  // every step issues the same loads) are loaded one step ahead.
-  // VEC: ldf >= n_cols rounded up to 16, so a step's 16 columns are always inside the row:
-  // the step start is clamped to the last step and each lane reads its 4 columns as two
-  // 16-byte loads (columns past n_cols are never inserted: process() checks c < n_cols).
-  const int last_step = ((n_cols - 1) / 16) * 16;
-  auto load_step = [&](int it, float(&af)[Q], double(&f)[NG][4]) __attribute__((always_inline)) {
-    if constexpr (D > 0) {
-      const int jc = it + ul < n_cols ? item_begin + it + ul : item_begin + n_cols - 1;
-      load_frag<Q>(ei + (int64_t)jc * D + gq * Q, af);
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int64_t row = ubase + g * 16 + ul;
-      const double *fr = F + (row < n_rows ? row : n_rows - 1) * ldf;
-      if constexpr (VEC) {
-        const int c0 = (it < last_step ? it : last_step) + gq * 4;
-        const double2 a = *reinterpret_cast<const double2 *>(fr + c0);
-        const double2 b = *reinterpret_cast<const double2 *>(fr + c0 + 2);
-        f[g][0] = a.x;
-        f[g][1] = a.y;
-        f[g][2] = b.x;
-        f[g][3] = b.y;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = it + gq * 4 + r;
-          f[g][r] = fr[c < n_cols ? c : n_cols - 1];
-        }
-      }
-    }
-  };
-  auto process = [&](int it, const float(&af)[Q], const double(&f)[NG][4]) __attribute__((always_inline)) {
-    double v[NG][4];
-    if constexpr (D > 0) {
-      f32x4 acc[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < Q; ++s)
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], uf[g][s], acc[g], 0, 0, 0);
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[g][r] = (double)acc[g][r] * f[g][r];
-    } else {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[g][r] = f[g][r];
-    }
-    // fast filter: one ballot per step; the exact per-column insertion only on a hit
-    const int c0 = it + gq * 4;
-    bool any = false;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) any |= v[g][r] > thr[g];
-    if (__ballot(any)) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool cand = c0 + r < n_cols && v[g][r] > thr[g];
-          const uint64_t bal = __ballot(cand);
-          if (bal) {
-            const int p = cnt[g] + __popcll(bal & same_user & lanemask_lt());
-            if (cand) {
-              cs[wave][g][ul][p] = v[g][r];
-              ci[wave][g][ul][p] = item_begin + c0 + r;
-            }
-            cnt[g] += __popcll(bal & same_user);
-            dirty[g] |= (bal & same_user) != 0;
-          }
-        }
-      }
-    }
-    bool over = false;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) over |= cnt[g] > S - 16;
-    if (__ballot(over)) {
-      const int lim = item_begin + (it + 16 < n_cols ? it + 16 : n_cols);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        uint64_t need = __ballot(cnt[g] > S - 16) & 0xffffull;
-        if (need) {
-          wave_sync();
-          while (need) {
-            const int u = __ffsll((long long)need) - 1;
-            need &= need - 1;
-            compact_user(g, u, lim);
-          }
-        }
-      }
-    }
-  };
-
-  // ring of 4 register buffers: the loads of step t+3 are in flight while step t is
-  // processed (F comes from HBM and is not shared between waves, so the wave needs its
-  // own memory-level parallelism); past the end the loads are clamped and harmless
-  float af0[Q], af1[Q], af2[Q], af3[Q];
-  double f0[NG][4], f1[NG][4], f2[NG][4], f3[NG][4];
-  load_step(0, af0, f0);
-  load_step(16, af1, f1);
-  load_step(32, af2, f2);
-  for (int it = 0;; it += 64) {
-    load_step(it + 48, af3, f3);
-    process(it, af0, f0);
-    if (it + 16 >= n_cols) break;
-    load_step(it + 64, af0, f0);
-    process(it + 16, af1, f1);
-    if (it + 32 >= n_cols) break;
-    load_step(it + 80, af1, f1);
-    process(it + 32, af2, f2);
-    if (it + 48 >= n_cols) break;
-    load_step(it + 96, af2, f2);
-    process(it + 48, af3, f3);
-    if (it + 64 >= n_cols) break;
-  }
-
-  wave_sync();
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    for (int u = 0; u < 16; ++u) {
-      const int64_t r = ubase + g * 16 + u;
-      if (r >= n_rows) break;
-      if (!__shfl((int)dirty[g], u)) continue;  // list as loaded: nothing to compact or store
-      compact_user(g, u, lim_end);
-      const int nc = __shfl(cnt[g], u);
-      for (int e = lane; e < k; e += 64) {
-        const double v = e < nc ? cs[wave][g][u][e] : neg_inf<double>();
-        const bool ok = e < nc && v != neg_inf<double>();  // dropped entries never surface
-        io_val[r * k + e] = ok ? v : neg_inf<double>();
-        io_idx[r * k + e] = ok ? ci[wave][g][u][e] : -1;
-      }
-      wave_sync();
-    }
-  }
-}
-
-#endif  // LG_REFERENCE_PATHS
 
 // ------------------------------------------------------------ the tile walk kernel
 // One launch per tile. Persistent waves (NW per workgroup, one workgroup per CU; each wave
@@ -1797,8 +600,8 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
 #pragma unroll
             for (int h0 = 0; h0 < Qd; h0 += H) {
               float av[H], bv[H];
-              load_frag<H>(ir + h0, av);
-              load_frag<H>(ur + h0, bv);
+              load_piece<H>(ir + h0, av);
+              load_piece<H>(ur + h0, bv);
 #pragma unroll
               for (int s = 0; s < H; ++s)
                 sc4 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], sc4, 0, 0, 0);
@@ -2088,345 +891,9 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
   }
 }
 
-#if LG_REFERENCE_PATHS
-template <int D, bool VEC>
-static void launch_tile_topk_v(int M, const double *F, int64_t ldf, int64_t n_rows, int32_t j0,
-                               int32_t n_cols, const float *eu, const float *ei,
-                               const int64_t *ex_rowptr, const int32_t *ex_col, int drop,
-                               int k, int first, double *io_val, int64_t *io_idx,
-                               hipStream_t s) {
-  // LDS per block (2 waves): 2 * NG * 16 * S * 12 B (+ 512 B) = 48 KiB (M=1, NG=2, S=64;
-  // 3 blocks = 6 waves per CU), 30 KiB at S=40 (k <= 24: 8 waves per CU, VGPR-limited; the
-  // list is compacted once it holds more than S-16 entries, so the first span of a walk,
-  // where most columns enter, keeps S=64), 48 KiB (M=2), 96 KiB (M=4). Measured per 4096-
-  // column span at 1M users: S=40 8.4-8.6 ms vs S=64 8.8-9.1 ms after the first spans,
-  // 26.4 vs 16.7 ms on the first.
-  if (M == 1 && k <= 24 && !first) {
-    const unsigned b = (unsigned)((n_rows + 63) / 64);
-    k_tile_topk<D, 2, 1, VEC, 40><<<b, 128, 0, s>>>(F, ldf, n_rows, j0, n_cols, eu, ei,
-                                                    ex_rowptr, ex_col, drop, k, first, io_val,
-                                                    io_idx);
-  } else if (M == 1) {
-    const unsigned b = (unsigned)((n_rows + 63) / 64);
-    k_tile_topk<D, 2, 1, VEC, 64><<<b, 128, 0, s>>>(F, ldf, n_rows, j0, n_cols, eu, ei,
-                                                    ex_rowptr, ex_col, drop, k, first, io_val,
-                                                    io_idx);
-  } else if (M == 2) {
-    const unsigned b = (unsigned)((n_rows + 31) / 32);
-    k_tile_topk<D, 1, 2, VEC, 128><<<b, 128, 0, s>>>(F, ldf, n_rows, j0, n_cols, eu, ei,
-                                                     ex_rowptr, ex_col, drop, k, first, io_val,
-                                                     io_idx);
-  } else {
-    const unsigned b = (unsigned)((n_rows + 31) / 32);
-    k_tile_topk<D, 1, 4, VEC, 256><<<b, 128, 0, s>>>(F, ldf, n_rows, j0, n_cols, eu, ei,
-                                                     ex_rowptr, ex_col, drop, k, first, io_val,
-                                                     io_idx);
-  }
-}
-
-template <int D>
-static void launch_tile_topk(int M, const double *F, int64_t ldf, int64_t n_rows, int32_t j0,
-                             int32_t n_cols, const float *eu, const float *ei,
-                             const int64_t *ex_rowptr, const int32_t *ex_col, int drop, int k,
-                             int first, double *io_val, int64_t *io_idx, hipStream_t s) {
-  // 16-byte F reads need rows padded to whole steps. (An inline-asm buffer-load form of the
-  // ring with hand-counted waits was measured no faster: 9.2 vs 8.9 ms per 4096-column span.)
-  const bool vec = ldf >= ((int64_t)n_cols + 15) / 16 * 16 && (ldf % 2) == 0 &&
-                   ((uintptr_t)F % 16) == 0;
-  if (vec)
-    launch_tile_topk_v<D, true>(M, F, ldf, n_rows, j0, n_cols, eu, ei, ex_rowptr, ex_col, drop, k,
-                             first, io_val, io_idx, s);
-  else
-    launch_tile_topk_v<D, false>(M, F, ldf, n_rows, j0, n_cols, eu, ei, ex_rowptr, ex_col, drop, k,
-                             first, io_val, io_idx, s);
-}
-
-#endif  // LG_REFERENCE_PATHS
-
-// Merge n_lists sorted top-K lists per row ([n_lists][n_rows][k], index -1 = empty) into one
-// ([n_rows][k]): the item-range shards of a multi-GPU spreading run. One wave per row, the
-// candidate list in LDS (CAP = 64*M >= k + 64), compacted by the wave-wide bitonic sort.
-template <int M>
-__global__ __launch_bounds__(256) void k_lists_merge_f64(const double *__restrict__ in_val,
-                                                         const int64_t *__restrict__ in_idx,
-                                                         int n_lists, int64_t n_rows, int k,
-                                                         double *__restrict__ out_val,
-                                                         int64_t *__restrict__ out_idx) {
-  constexpr int CAP = 64 * M;
-  __shared__ double cs[4][CAP];
-  __shared__ int ci[4][CAP];
-  const int wave = threadIdx.x / 64;
-  const int lane = lane_id();
-  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
-  if (row >= n_rows) return;
-  int cnt = 0;
-  double tau = neg_inf<double>();
-  int tau_id = kPadId;
-  for (int s = 0; s < n_lists; ++s) {
-    const int64_t base = ((int64_t)s * n_rows + row) * k;
-    for (int e0 = 0; e0 < k; e0 += 64) {
-      const int e = e0 + lane;
-      double v = neg_inf<double>();
-      int id = -1;
-      if (e < k) {
-        const int64_t x = in_idx[base + e];
-        if (x >= 0) {
-          v = in_val[base + e];
-          id = (int)x;
-        }
-      }
-      const bool cand = id >= 0 && before(v, id, tau, tau_id);
-      const uint64_t bal = __ballot(cand);
-      const int pos = cnt + __popcll(bal & lanemask_lt());
-      if (cand) {
-        cs[wave][pos] = v;
-        ci[wave][pos] = id;
-      }
-      cnt += __popcll(bal);
-      if (cnt > CAP - 64) {
-        wave_sync();
-        cnt = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-      }
-    }
-  }
-  wave_sync();
-  const int nc = wave_compact<double, M>(cs[wave], ci[wave], cnt, k, tau, tau_id);
-  for (int e = lane; e < k; e += 64) {
-    out_val[row * k + e] = e < nc ? cs[wave][e] : neg_inf<double>();
-    out_idx[row * k + e] = e < nc ? ci[wave][e] : -1;
-  }
-}
-
 }  // namespace lg
 
 using namespace lg;
-
-extern "C" int lg_spread_tile_seek(const int64_t *user_rowptr, const int32_t *user_items,
-                                   int64_t n_users, int32_t item_begin, int64_t *cur,
-                                   lg_stream_t stream) {
-  LG_REQUIRE(user_rowptr && cur && n_users >= 0 && item_begin >= 0,
-             "lg_spread_tile_seek: bad arguments");
-  if (n_users == 0) return LG_OK;
-  k_tile_seek<<<dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-      user_rowptr, user_items, n_users, item_begin, cur);
-  return launch_status("lg_spread_tile_seek");
-}
-
-extern "C" int lg_topk_lists_merge_f64(const double *in_val, const int64_t *in_idx,
-                                       int32_t n_lists, int64_t n_rows, int32_t k,
-                                       double *out_val, int64_t *out_idx, lg_stream_t stream) {
-  LG_REQUIRE(n_lists >= 1 && n_rows >= 0, "lg_topk_lists_merge_f64: bad sizes");
-  LG_REQUIRE(k >= 1 && k <= 128, "lg_topk_lists_merge_f64: k=%d not in [1,128]", k);
-  LG_REQUIRE(n_rows == 0 || (in_val && in_idx && out_val && out_idx),
-             "lg_topk_lists_merge_f64: NULL argument");
-  if (n_rows == 0) return LG_OK;
-  const dim3 grid((unsigned)((n_rows + 3) / 4));
-  hipStream_t s = (hipStream_t)stream;
-  if (k <= 64)
-    k_lists_merge_f64<2><<<grid, dim3(256), 0, s>>>(in_val, in_idx, n_lists, n_rows, k, out_val,
-                                                    out_idx);
-  else
-    k_lists_merge_f64<4><<<grid, dim3(256), 0, s>>>(in_val, in_idx, n_lists, n_rows, k, out_val,
-                                                    out_idx);
-  return launch_status("lg_topk_lists_merge_f64");
-}
-
-extern "C" int lg_hybrid_recip_f64(const double *k_item, int64_t n_items, double lambda,
-                                   double *ra, double *rb, lg_stream_t stream) {
-  LG_REQUIRE(k_item && ra && rb && n_items >= 0, "lg_hybrid_recip_f64: bad arguments");
-  if (n_items == 0) return LG_OK;
-  k_hybrid_recip<<<dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0,
-                   (hipStream_t)stream>>>(k_item, n_items, lambda, ra, rb);
-  return launch_status("lg_hybrid_recip_f64");
-}
-
-extern "C" int lg_inv_degree_f64(const int64_t *rowptr, int64_t n_rows, double *inv,
-                                 lg_stream_t stream) {
-  LG_REQUIRE(rowptr && inv && n_rows >= 0, "lg_inv_degree_f64: bad arguments");
-  if (n_rows == 0) return LG_OK;
-  k_inv_degree<<<dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-      rowptr, n_rows, inv);
-  return launch_status("lg_inv_degree_f64");
-}
-
-#if LG_REFERENCE_PATHS
-extern "C" int lg_spread_tile_cursor(const int64_t *user_rowptr, const int32_t *user_items,
-                                     int64_t n_users, int32_t item_end, const int64_t *cur,
-                                     int64_t *end, uint16_t *count, lg_stream_t stream) {
-  LG_REQUIRE(user_rowptr && cur && end && count && n_users >= 0 && cur != end,
-             "lg_spread_tile_cursor: bad arguments");
-  if (n_users == 0) return LG_OK;
-  k_tile_cursor<<<dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0,
-                  (hipStream_t)stream>>>(user_rowptr, user_items, n_users, item_end, cur, end,
-                                         count);
-  return launch_status("lg_spread_tile_cursor");
-}
-
-extern "C" int lg_spread_tile_bound(const int64_t *item_rowptr, const int32_t *item_users,
-                                    int64_t n_items, const uint16_t *count, int64_t *bound,
-                                    lg_stream_t stream) {
-  LG_REQUIRE(item_rowptr && count && bound && n_items >= 0,
-             "lg_spread_tile_bound: bad arguments");
-  if (n_items == 0) return LG_OK;
-  k_tile_bound<<<dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
-      item_rowptr, item_users, n_items, count, bound);
-  return launch_status("lg_spread_tile_bound");
-}
-
-extern "C" size_t lg_spread_tile_rows_ws_bytes(int64_t n_items) {
-  return (size_t)(n_items + 1) * sizeof(int64_t);  // hub count + hub row list
-}
-
-extern "C" int lg_spread_tile_rows_f64(const int64_t *item_rowptr, const int32_t *item_users,
-                                       const int32_t *user_items, const uint16_t *user_cls,
-                                       const double *inv_deg, int64_t n_items,
-                                       const int64_t *cur, const uint16_t *count,
-                                       int32_t item_begin, int32_t tile, const int64_t *bound,
-                                       int64_t vthr, const int64_t *ovf_ptr, void *lines,
-                                       void *ovf, int32_t *row_len, void *ws, size_t ws_bytes,
-                                       lg_stream_t stream) {
-  LG_REQUIRE(item_rowptr && user_cls && inv_deg && cur && count && bound && ovf_ptr && lines &&
-                 ovf && n_items >= 0 && vthr >= kLineSlots,
-             "lg_spread_tile_rows_f64: bad arguments");
-  LG_REQUIRE(tile >= 1 && tile <= 8192 && item_begin >= 0,
-             "lg_spread_tile_rows_f64: tile %d not in [1, 8192]", tile);
-  if (n_items == 0) return LG_OK;
-  const size_t need = lg_spread_tile_rows_ws_bytes(n_items);
-  if (!ws || ws_bytes < need) {
-    set_error("lg_spread_tile_rows_f64: workspace %zu < %zu bytes", ws_bytes, need);
-    return LG_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  int64_t *n_hub = (int64_t *)ws;
-  int64_t *hub_rows = n_hub + 1;
-  if (hipMemsetAsync(n_hub, 0, sizeof(int64_t), s) != hipSuccess) {
-    set_error("lg_spread_tile_rows_f64: hipMemsetAsync failed");
-    return LG_ERR_HIP;
-  }
-  k_tile_rows<<<dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s>>>(
-      item_rowptr, item_users, user_items, user_cls, n_items, cur, count, item_begin, bound, vthr,
-      ovf_ptr, (uint32_t *)lines, (uint32_t *)ovf, row_len);
-  k_hub_list<<<dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, s>>>(
-      bound, n_items, vthr, (unsigned long long *)n_hub, hub_rows);
-  k_tile_rows_hub<<<dim3(1024), dim3(256), (size_t)tile * sizeof(double), s>>>(
-      hub_rows, n_hub, item_rowptr, item_users, user_items, inv_deg, cur, count, item_begin, tile,
-      ovf_ptr, (uint32_t *)lines, (uint32_t *)ovf, row_len);
-  return launch_status("lg_spread_tile_rows_f64");
-}
-
-#endif  // LG_REFERENCE_PATHS
-
-extern "C" int lg_spread_group_cursor(const int64_t *user_rowptr, const int32_t *user_items,
-                                      const uint16_t *user_cls, int64_t n_users,
-                                      int32_t group_begin, int32_t tile, int32_t n_tiles,
-                                      int32_t stop, const int64_t *cur, int64_t *end,
-                                      uint16_t *counts, void *rec, lg_stream_t stream) {
-  LG_REQUIRE(user_rowptr && user_cls && cur && end && counts && rec && n_users >= 0 &&
-                 cur != end && group_begin >= 0 && stop > group_begin,
-             "lg_spread_group_cursor: bad arguments");
-  LG_REQUIRE(((uintptr_t)rec & 15) == 0, "lg_spread_group_cursor: rec not 16-byte aligned");
-  LG_REQUIRE(tile >= 1 && tile <= 8192 && n_tiles >= 1 && n_tiles <= kGroupMax &&
-                 (n_tiles <= kGroupWide || tile <= 4096),
-             "lg_spread_group_cursor: tile %d / n_tiles %d (groups of more than %d tiles need tile <= 4096)",
-             tile, n_tiles, kGroupWide);
-  LG_REQUIRE(((uintptr_t)counts & 15) == 0, "lg_spread_group_cursor: counts not 16-byte aligned");
-  if (n_users == 0) return LG_OK;
-  k_group_cursor<<<dim3((unsigned)((n_users + 255) / 256)), dim3(256), 0,
-                   (hipStream_t)stream>>>(user_rowptr, user_items, user_cls, n_users,
-                                          group_begin, tile, n_tiles, stop, cur, end,
-                                          (uint4 *)counts, (uint4 *)rec);
-  return launch_status("lg_spread_group_cursor");
-}
-
-extern "C" int lg_spread_group_bound(const int64_t *item_rowptr, const int32_t *item_users,
-                                     int64_t n_items, const uint16_t *counts, int32_t n_tiles,
-                                     int64_t *bound, lg_stream_t stream) {
-  LG_REQUIRE(item_rowptr && counts && bound && n_items >= 0 && n_tiles >= 1 &&
-                 n_tiles <= kGroupMax && ((uintptr_t)counts & 15) == 0,
-             "lg_spread_group_bound: bad arguments");
-  if (n_items == 0) return LG_OK;
-  k_group_bound<<<dim3((unsigned)((n_items + 15) / 16)), dim3(256), 0, (hipStream_t)stream>>>(
-      item_rowptr, item_users, n_items, (const uint4 *)counts, n_tiles, bound);
-  return launch_status("lg_spread_group_bound");
-}
-
-extern "C" int lg_spread_group_units(const int64_t *bound, int64_t n_items, int32_t group_begin,
-                                     int32_t tile, int32_t n_tiles, int32_t stop, int64_t vthr,
-                                     int64_t *units, lg_stream_t stream) {
-  LG_REQUIRE(bound && units && n_items >= 0 && group_begin >= 0 && stop > group_begin &&
-                 vthr >= kLineSlots,
-             "lg_spread_group_units: bad arguments");
-  LG_REQUIRE(tile >= 1 && tile <= 8192 && n_tiles >= 1 && n_tiles <= kGroupMax &&
-                 (n_tiles <= kGroupWide || tile <= 4096),
-             "lg_spread_group_units: tile %d / n_tiles %d (groups of more than %d tiles need tile <= 4096)",
-             tile, n_tiles, kGroupWide);
-  const int64_t n = n_items * n_tiles;
-  if (n == 0) return LG_OK;
-  k_group_units<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
-      bound, n_items, group_begin, tile, n_tiles, stop, vthr, units);
-  return launch_status("lg_spread_group_units");
-}
-
-extern "C" size_t lg_spread_group_rows_ws_bytes(int64_t n_items, int32_t n_tiles) {
-  return (size_t)(n_items * (n_tiles > 0 ? n_tiles : 1) + 1) * sizeof(int64_t);
-}
-
-extern "C" int lg_spread_group_rows_f64(
-    const int64_t *item_rowptr, const int32_t *item_users, const int32_t *user_items,
-    const double *inv_deg, int64_t n_items, const int64_t *cur, const uint16_t *counts,
-    const void *rec, int32_t group_begin, int32_t tile, int32_t n_tiles, int32_t stop,
-    const int64_t *bound, int64_t vthr, const int64_t *units_incl, void *lines, void *ovf,
-    int32_t *row_len, void *ws, size_t ws_bytes, lg_stream_t stream) {
-  LG_REQUIRE(item_rowptr && rec && inv_deg && cur && counts && bound && units_incl &&
-                 lines && ovf && n_items >= 0 && group_begin >= 0 && stop > group_begin,
-             "lg_spread_group_rows_f64: bad arguments");
-  LG_REQUIRE(vthr >= kLineSlots && vthr < 65536,
-             "lg_spread_group_rows_f64: vthr %lld not in [31, 65535]", (long long)vthr);
-  LG_REQUIRE(tile >= 1 && tile <= 8192 && n_tiles >= 1 && n_tiles <= kGroupMax &&
-                 (n_tiles <= kGroupWide || tile <= 4096),
-             "lg_spread_group_rows_f64: tile %d / n_tiles %d (groups of more than %d tiles need tile <= 4096)",
-             tile, n_tiles, kGroupWide);
-  LG_REQUIRE(((uintptr_t)counts & 15) == 0, "lg_spread_group_rows_f64: counts not 16-byte aligned");
-  if (n_items == 0) return LG_OK;
-  const size_t need = lg_spread_group_rows_ws_bytes(n_items, n_tiles);
-  if (!ws || ws_bytes < need) {
-    set_error("lg_spread_group_rows_f64: workspace %zu < %zu bytes", ws_bytes, need);
-    return LG_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  int64_t *n_hub = (int64_t *)ws;
-  int64_t *hub_rows = n_hub + 1;
-  if (hipMemsetAsync(n_hub, 0, sizeof(int64_t), s) != hipSuccess) {
-    set_error("lg_spread_group_rows_f64: hipMemsetAsync failed");
-    return LG_ERR_HIP;
-  }
-  const uint4 *c4 = (const uint4 *)counts;
-  k_group_rows<<<dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s>>>(
-      item_rowptr, item_users, user_items, n_items, c4, (const uint4 *)rec, group_begin, tile,
-      n_tiles, stop, bound, vthr, units_incl, (uint32_t *)lines, (uint32_t *)ovf, row_len);
-  const int64_t nflat = n_items * n_tiles;
-  k_hub_list<<<dim3((unsigned)((nflat + 255) / 256)), dim3(256), 0, s>>>(
-      bound, nflat, vthr, (unsigned long long *)n_hub, hub_rows);
-  const int hub_waves = tile <= 4096 ? 4 : 2;  // (LDS: one tile of doubles per wave)
-  k_group_rows_hub<<<dim3(1024), dim3(64 * hub_waves), (size_t)hub_waves * tile * sizeof(double),
-                     s>>>(
-      hub_rows, n_hub, item_rowptr, item_users, user_items, inv_deg, n_items, cur, c4,
-      group_begin, tile, stop, bound, vthr, units_incl, (uint32_t *)lines, (uint32_t *)ovf,
-      row_len);
-  return launch_status("lg_spread_group_rows_f64");
-}
-
-static int n_cus() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n_cu <= 0)
-      n_cu = 256;
-  }
-  return n_cu;
-}
 
 // waves per workgroup: as many as the LDS holds next to the shared tables (<= 8), one
 // workgroup per CU, persistent
@@ -2442,7 +909,8 @@ static int launch_walk(const WalkArgs &a, hipStream_t s) {
     return LG_ERR_ARG;
   }
   const int64_t want = (a.n_users + nw - 1) / nw;
-  const int64_t cap = n_cus();
+  const int cus = device_cus();
+  const int64_t cap = cus > 0 ? cus : 256;
   const unsigned blocks = (unsigned)(want < cap ? want : cap);
   const size_t lds = shared + (size_t)nw * per;
   bool seeded = false;
@@ -2455,75 +923,6 @@ static int launch_walk(const WalkArgs &a, hipStream_t s) {
   if (!seeded) k_tile_walk<MODE, D, M><<<dim3(blocks), dim3(64 * nw), lds, s>>>(a);
   return LG_OK;
 }
-
-#if LG_REFERENCE_PATHS
-extern "C" int lg_spread_tile_resource_f64(const int64_t *user_rowptr,
-                                           const int32_t *user_items, const double *ra_edge,
-                                           int64_t n_users, const void *lines, const void *ovf,
-                                           int32_t null_row,
-                                           const double *rbeta, const double *inv_cls,
-                                           int32_t item_begin, int32_t tile, int32_t width,
-                                           double *F, int64_t ldf, lg_stream_t stream) {
-  LG_REQUIRE(user_rowptr && user_items && ra_edge && lines && ovf && rbeta && inv_cls && F &&
-                 n_users >= 0 && ldf >= tile,
-             "lg_spread_tile_resource_f64: bad arguments");
-  LG_REQUIRE(tile >= 1 && tile <= 8192 && width >= 1 && width <= tile,
-             "lg_spread_tile_resource_f64: tile %d / width %d", tile, width);
-  LG_REQUIRE(null_row >= 0 && null_row < (1 << 25) - 1,
-             "tile walk: %d items exceed the 32-bit line offsets", null_row);
-  if (n_users == 0) return LG_OK;
-  WalkArgs a{};
-  a.user_rowptr = user_rowptr;
-  a.user_items = user_items;
-  a.ra_edge = ra_edge;
-  a.n_users = n_users;
-  a.lines = (const uint4 *)lines;
-  a.ovf = (const uint4 *)ovf;
-  a.null_row = null_row;
-  a.item_begin = item_begin;
-  a.tile = tile;
-  a.width = width;
-  a.rbeta = rbeta;
-  a.g_inv = inv_cls;
-  a.F = F;
-  a.ldf = ldf;
-  const int st = launch_walk<MODE_F, 0, 1>(a, (hipStream_t)stream);
-  if (st != LG_OK) return st;
-  return launch_status("lg_spread_tile_resource_f64");
-}
-
-extern "C" int lg_tile_topk_f64(const double *F, int64_t ldf, int64_t n_rows,
-                                int32_t item_begin, int32_t n_cols, const float *eu,
-                                const float *ei, int32_t dim, const int64_t *ex_rowptr,
-                                const int32_t *ex_col, int32_t excl_mode, int32_t k,
-                                int32_t first, double *io_val, int64_t *io_idx,
-                                lg_stream_t stream) {
-  LG_REQUIRE(F && io_val && io_idx && n_rows >= 0 && n_cols >= 1 && ldf >= n_cols &&
-                 item_begin >= 0 && (int64_t)item_begin + n_cols < 0x7fffffff,
-             "lg_tile_topk_f64: bad arguments");
-  LG_REQUIRE(k >= 1 && k <= 128, "lg_tile_topk_f64: k=%d not in [1,128]", k);
-  LG_REQUIRE(!eu == !ei, "lg_tile_topk_f64: eu/ei must both be set or both NULL");
-  LG_REQUIRE(!eu || dim == 32 || dim == 64 || dim == 128,
-             "lg_tile_topk_f64: dim %d not in {32,64,128}", dim);
-  LG_REQUIRE(excl_mode == LG_EXCL_DROP || excl_mode == LG_EXCL_NONE,
-             "lg_tile_topk_f64: bad excl_mode %d", excl_mode);
-  LG_REQUIRE(!ex_rowptr == !ex_col, "lg_tile_topk_f64: ex_rowptr/ex_col must both be set");
-  LG_REQUIRE(!(eu && excl_mode == LG_EXCL_NONE && ex_rowptr),
-             "lg_tile_topk_f64: a G factor with exclusions requires LG_EXCL_DROP");
-  if (n_rows == 0) return LG_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int M = k <= 32 ? 1 : (k <= 64 ? 2 : 4);
-  const int drop = excl_mode == LG_EXCL_DROP;
-  switch (eu ? dim : 0) {
-    case 0: launch_tile_topk<0>(M, F, ldf, n_rows, item_begin, n_cols, eu, ei, ex_rowptr, ex_col, drop, k, first, io_val, io_idx, s); break;
-    case 32: launch_tile_topk<32>(M, F, ldf, n_rows, item_begin, n_cols, eu, ei, ex_rowptr, ex_col, drop, k, first, io_val, io_idx, s); break;
-    case 64: launch_tile_topk<64>(M, F, ldf, n_rows, item_begin, n_cols, eu, ei, ex_rowptr, ex_col, drop, k, first, io_val, io_idx, s); break;
-    default: launch_tile_topk<128>(M, F, ldf, n_rows, item_begin, n_cols, eu, ei, ex_rowptr, ex_col, drop, k, first, io_val, io_idx, s); break;
-  }
-  return launch_status("lg_tile_topk_f64");
-}
-
-#endif  // LG_REFERENCE_PATHS
 
 extern "C" size_t lg_spread_tile_resource_topk_lds_bytes(int32_t tile, int32_t k, int32_t dim) {
   // one wave's share plus the workgroup's tables (the launch fits as many waves as it can)
@@ -2613,4 +1012,3 @@ extern "C" int lg_spread_tile_resource_topk_f64(
   if (st != LG_OK) return st;
   return launch_status("lg_spread_tile_resource_topk_f64");
 }
-

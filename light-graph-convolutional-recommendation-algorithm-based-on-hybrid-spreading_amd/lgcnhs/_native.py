@@ -217,7 +217,7 @@ def lib() -> ctypes.CDLL:
 
 def ref_lib() -> ctypes.CDLL:
     """The test-reference build (lib/liblgcnhs_ref.so: the product library plus the
-    per-tile reference paths of include/lgcnhs_ref.h), for tests only; its entry points
+    per-tile reference paths of include/lgcnhs_ref.h, csrc/spread_ref.hip), for tests only; its entry points
     report errors through its own lg_last_error (use ref_check)."""
     global _ref
     with _lock:

@@ -902,7 +902,7 @@ def spread_topk(A: Interactions, W: torch.Tensor, k: int, excl: RowSets | None,
 
 
 # ------------------------------------------------------------------- factored spreading
-INV_TAB = 512      # degree classes cached in LDS by the walk (csrc/spread_tiled.hip)
+INV_TAB = 512      # degree classes cached in LDS by the walk (kInvTab, csrc/tile_lines.h)
 MAX_CLASSES = 0x7FFF   # P slot words keep bit 31 clear (it marks V entries)
 LINE_SLOTS, LINE_ENTS = 31, 7   # P slots / V entries in a row's 128-byte line
 GROUP_MAX, GROUP_WIDE = 16, 8   # tiles per group build (tiles wider than 4096: 8)
@@ -935,7 +935,7 @@ class HybridScale:
 
 def degree_classes(deg: torch.Tensor):
     """(1-based class of each row's degree as uint16, fp64 table inv[c] = fl(1/k) of class
-    c, inv[0] = 0): the slot code of the P rows of csrc/spread_tiled.hip. Classes are
+    c, inv[0] = 0): the slot code of the P rows of csrc/tile_lines.h. Classes are
     numbered by how many rows have the degree, so the common ones fall in the walk's LDS
     table (c < 512). Rows of degree 0 get class 0 (they are in no pair)."""
     dev = deg.device
@@ -967,7 +967,7 @@ def _run_units(length: torch.Tensor, hub: torch.Tensor) -> torch.Tensor:
 
 
 class TileWeights:
-    """general_W restricted to one item tile, in the line format of csrc/spread_tiled.hip
+    """general_W restricted to one item tile, in the line format of csrc/tile_lines.h
     (lg_spread_tile_rows_f64: one 128-byte line per item row at 128 * i, plus overflow runs;
     P rows = the (user, item) pairs behind the row as 4-byte slots, V rows = the merged fp64
     general_W values of hub items). The tile itself is lambda-independent; ``lam`` sets the

@@ -23,6 +23,7 @@ fi
 patch -s $W < "$PATCH"
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -I$R/include -I$C"
 /opt/rocm/bin/hipcc $F -x hip -c $W -o $C/../build/ab/${SRC}_$1.o
-OBJS=$(ls $C/../build/*.o | grep -v "/$SRC.o")
+# (spread_ref.o is the reference library's stand-in for spread_tiled.o: never beside it)
+OBJS=$(ls $C/../build/*.o | grep -v "/$SRC.o" | grep -v "/spread_ref.o")
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $OBJS $C/../build/ab/${SRC}_$1.o -o $C/../lib/ab/liblgcnhs_$1.so
 echo "built lib/ab/liblgcnhs_$1.so from $2 (base ${BASE:-working tree})"

@@ -1,5 +1,5 @@
 """Test-only reference paths of the factored spreading (K3s), on lib/liblgcnhs_ref.so (the
-product library built with -DLG_REFERENCE_PATHS=1, include/lgcnhs_ref.h): the per-tile build
+product library plus csrc/spread_ref.hip, include/lgcnhs_ref.h): the per-tile build
 passes (lg_spread_tile_cursor / _bound / _rows_f64), the F-writing walk
 (lg_spread_tile_resource_f64) and the two-kernel top-K merge (lg_tile_topk_f64). The product
 (lgcnhs.ops) builds tiles a group at a time and walks them fused; these are the bitwise

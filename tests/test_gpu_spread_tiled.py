@@ -275,6 +275,31 @@ def test_topk_lists_merge_vs_oracle(k, L):
     assert np.array_equal(ov.cpu().numpy(), ev)
 
 
+@pytest.mark.parametrize("k", [64, 65])
+@pytest.mark.parametrize("n", [1, 5])
+def test_topk_lists_merge_register_seam_ragged_rows(k, n):
+    """lg_topk_lists_merge_f64 on either side of the seam between its two register-sorted
+    lists (k = 64: 128 entries, k = 65: 256) with row counts that leave a block of four waves
+    partly idle (the idle waves leave at row >= n_rows): two lists with empty (-1) slots at
+    their ends and ties across the lists, against the lexsort of the union."""
+    from lgcnhs import ops
+    rng = np.random.default_rng(1000 * k + n)
+    L = 2
+    vals = np.full((L, n, k), -np.inf)
+    idxs = np.full((L, n, k), -1, np.int64)
+    for l in range(L):
+        for r in range(n):
+            m = k if (l + r) % 2 == 0 else k - 1 - 7 * r  # a full list beside one with -1 slots
+            ids = rng.choice(np.arange(l * 1000, (l + 1) * 1000), size=m, replace=False)
+            v = rng.integers(0, 6, size=m).astype(np.float64) * 0.25  # many ties
+            o = np.lexsort((ids, -v))
+            vals[l, r, :m], idxs[l, r, :m] = v[o], ids[o]
+    ov, oi = ops.merge_topk_lists(torch.as_tensor(vals).to(DEV), torch.as_tensor(idxs).to(DEV))
+    ev, ei = _np_merge(vals, idxs, k)
+    assert np.array_equal(oi.cpu().numpy(), ei)
+    assert np.array_equal(ov.cpu().numpy(), ev)
+
+
 def test_tile_seek_matches_searchsorted():
     from lgcnhs import ops
     A = _inter(400, 900, 9000, seed=4, zipf=True)
