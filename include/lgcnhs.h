@@ -380,6 +380,26 @@ int lg_rows_topk_wide_f64(const double *F, int64_t ldf, int64_t n_rows, int64_t 
                           const int64_t *ex_rowptr, const int32_t *ex_col, int32_t excl_mode,
                           int32_t k, double *out_val, int64_t *out_idx, lg_stream_t stream);
 
+/* lg_spread_resource_f64 + lg_rows_topk_(wide_)f64 over a candidate item set, fused: row r of
+ * the output is the first k (in [1, 1024]) of {(v(r, j), j) : j in item_ids[0..n_cand), j not
+ * dropped by r's exclusions} under (value desc, item id asc), v(r, j) = (G[r][j] *) F[r][j],
+ * F[r][j] = sum_{i in user_items of row r, ascending} W[i][j] over the full n_items x n_items
+ * W (a candidate set restricts the ranked columns, never the spreading), G as above
+ * (eu [n_rows, dim], ei [n_items, dim]: the full item table). item_ids: strictly ascending
+ * ids in [0, n_items), n_cand in [0, n_items] (0: every row is padding). Exclusion columns are
+ * item ids; modes, admission (NaN and -inf never rank) and the {-inf, -1} padding as
+ * lg_rows_topk_f64; out_idx holds item ids. Bit for bit lg_rows_topk_(wide_)f64 on the
+ * columns item_ids of lg_spread_resource_f64's F with ei[item_ids], the exclusions renumbered
+ * and the ids mapped back; no F, no gather, no workspace. Memory-safe on any list: an id
+ * outside [0, n_items) never ranks, a list that is not ascending gives unspecified lists. */
+int lg_spread_rows_topk_items_f64(const int64_t *user_rowptr, const int32_t *user_items,
+                                  const double *W, int64_t n_rows, int64_t n_items,
+                                  const int32_t *item_ids, int64_t n_cand,
+                                  const float *eu, const float *ei, int32_t dim,
+                                  const int64_t *ex_rowptr, const int32_t *ex_col,
+                                  int32_t excl_mode, int32_t k, double *out_val,
+                                  int64_t *out_idx, lg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Factored spreading over item tiles: the path for catalogs whose I x I general_W / W do
  * not fit (SURVEY.md §8 a9 "K3s"; C5 = 1M x 1M would need 8 TB per matrix). The values of

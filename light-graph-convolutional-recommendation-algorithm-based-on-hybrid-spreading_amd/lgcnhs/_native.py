@@ -120,6 +120,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     ),
+    "lg_spread_rows_topk_items_f64": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp,
+         _vp],
+    ),
     "lg_hybrid_recip_f64": (ctypes.c_int, [_vp, _i64, _f64, _vp, _vp, _vp]),
     "lg_inv_degree_f64": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
     "lg_spread_group_cursor": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,

@@ -484,7 +484,7 @@ def exchange_topk(vals: torch.Tensor, idxs: torch.Tensor, rank: int, world: int,
 def sharded_spread_topk(A, lam: float, k: int, excl, drop: bool = True, eu=None, ei=None,
                         rank: int = 0, world: int = 1, group=None, tile: int = 2048,
                         local_fn=None, merge_fn=None,
-                        stats: dict | None = None):
+                        stats: dict | None = None, items=None):
     """The LGCNHS recommendation (model/SpreadLightGCN/model.py:122-153 + recommend.py:18-52)
     over `world` GPUs, sharded by ITEM range: rank r builds only its own tiles of W
     (user-independent work is never repeated across ranks) and scores every user on them;
@@ -493,8 +493,15 @@ def sharded_spread_topk(A, lam: float, k: int, excl, drop: bool = True, eu=None,
     [u0, u1) of the single-GPU ops.spread_topk_tiled.
 
     local_fn / merge_fn default to the HIP path (ops.spread_topk_tiled /
-    ops.merge_topk_lists); tests substitute CPU stand-ins to run the exchange on gloo."""
+    ops.merge_topk_lists); tests substitute CPU stand-ins to run the exchange on gloo.
+
+    ``items`` (a candidate item set, ops.spread_topk_tiled's): not supported together with the
+    item-range shards -- anything but None raises."""
     from . import ops
+    if items is not None:
+        raise ValueError("sharded_spread_topk: a candidate item set (items=) cannot be combined "
+                         "with the item-range shards; call ops.spread_topk_tiled(items=...) on "
+                         "one device")
     local_fn = local_fn or ops.spread_topk_tiled
     merge_fn = merge_fn or ops.merge_topk_lists
     i0, i1 = item_range(A.n_items, tile, rank, world)

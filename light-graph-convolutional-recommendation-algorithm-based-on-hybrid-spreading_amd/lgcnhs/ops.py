@@ -14,6 +14,8 @@ spread_topk_tiled  the above over item tiles,      (same; for catalogs whose I x
                    never holding an I x I matrix    does not fit)
                    (k > 128: peeled passes of 128)
 spread_recommend   dense or tiled, whichever fits  model/SpreadMethod/recommend.py:59-115
+                   (items=: over a candidate item set -- csrc/rows_topk_items.hip on the
+                   dense path, a column view of the tiles on the tiled one)
 """
 from __future__ import annotations
 
@@ -924,11 +926,14 @@ def hybrid_recip(k_item: torch.Tensor, lam: float):
 class HybridScale:
     """The lambda-dependent side of the factored spreading: rb = 1/beta per item and
     ra_edge = 1/alpha of the item of every interaction, aligned with A.by_user.col (so the
-    walk reads a user's factors contiguously with its item ids)."""
+    walk reads a user's factors contiguously with its item ids). ``cols`` (a column view,
+    see TileWeights): rb of those items only, by position; ra_edge is row-side and stays."""
 
-    def __init__(self, A: "Interactions", lam: float):
+    def __init__(self, A: "Interactions", lam: float, cols: torch.Tensor | None = None):
         self.lam = float(lam)
         ra, self.rb = hybrid_recip(A.k_item, lam)
+        if cols is not None:
+            self.rb = self.rb[cols.to(torch.int64)]
         # one entry past the interactions: the walk's padding rows read it (never used)
         self.ra_edge = torch.cat([ra[A.by_user.col.to(torch.int64)], ra.new_zeros(1)])
 
@@ -979,15 +984,28 @@ class TileWeights:
     4096): lg_spread_group_cursor / _bound / _units / _rows_f64 visit each (item row, user)
     pair once per group instead of once per tile and write the group's tiles side by side; build(j0) of a tile inside the built
     group only selects it. Every tile's words are those of the per-tile reference build
-    (include/lgcnhs_ref.h) bit for bit (tests/test_gpu_spread_tiled.py)."""
+    (include/lgcnhs_ref.h) bit for bit (tests/test_gpu_spread_tiled.py).
+
+    ``cols`` (a column view: strictly ascending int32 item ids on the device, the candidate
+    set of spread_topk_tiled(items=...)): the tiles then hold the columns cols[0], cols[1], ..
+    of general_W, numbered by position -- tile t is positions [t tile, (t + 1) tile) and there
+    are ceil(len(cols) / tile) of them. The build kernels keep two id spaces apart: rows
+    (A.by_item, the row count n_items, inv_deg and the degree classes: the full graph, full
+    degrees) and columns (the user -> column CSR they cursor through, group_begin / tile /
+    stop), and only the second becomes A.by_user.restrict_cols(cols). Without ``cols`` the
+    column CSR is A.by_user itself and nothing is gathered."""
 
     def __init__(self, A: Interactions, lam: float, tile: int, vthr: int | None = None,
-                 group: int | None = None):
+                 group: int | None = None, cols: torch.Tensor | None = None):
         if not 1 <= tile <= 8192:
             raise ValueError(f"tile {tile} not in [1, 8192]")
         self.A, self.tile, self.lam = A, int(tile), float(lam)
         dev = A.k_item.device
         self.dev = dev
+        # the column side: user -> column sets and the column count
+        self.cols = cols
+        self.col_sets = A.by_user if cols is None else A.by_user.restrict_cols(cols)
+        self.n_cols = A.n_items if cols is None else int(cols.numel())
         if vthr is None:
             vthr = self.tile
         self.vthr = max(LINE_SLOTS, int(vthr))
@@ -1000,9 +1018,9 @@ class TileWeights:
         if self.vthr > 65535:
             raise ValueError(f"vthr {self.vthr} > 65535 (the group build counts 16-bit)")
         I = A.n_items
-        self.group = int(min(group, max(1, -(-I // self.tile))))
+        self.group = int(min(group, max(1, -(-self.n_cols // self.tile))))
         S = self.group
-        self.cur = A.by_user.rowptr[:-1].contiguous().clone()
+        self.cur = self.col_sets.rowptr[:-1].contiguous().clone()
         self.end = torch.empty_like(self.cur)
         # 16 uint16 per user (two 16-byte halves: tiles 0-7, 8-15) + the rows pass's 16-byte
         # records
@@ -1040,7 +1058,7 @@ class TileWeights:
     @property
     def scale(self) -> HybridScale:
         if self._scale is None:
-            self._scale = HybridScale(self.A, self.lam)
+            self._scale = HybridScale(self.A, self.lam, self.cols)
         return self._scale
 
     @property
@@ -1102,10 +1120,10 @@ class TileWeights:
     def seek(self, j0: int) -> None:
         """Start the tile walk at item j0 instead of 0 (an item-range shard): the next
         build() must be build(j0)."""
-        A = self.A
-        if not 0 <= j0 <= A.n_items:
-            raise ValueError(f"seek({j0}) outside [0, {A.n_items}]")
-        N.check(N.lib().lg_spread_tile_seek(N.ptr(A.by_user.rowptr), N.ptr(A.by_user.col),
+        A, cs = self.A, self.col_sets
+        if not 0 <= j0 <= self.n_cols:
+            raise ValueError(f"seek({j0}) outside [0, {self.n_cols}]")
+        N.check(N.lib().lg_spread_tile_seek(N.ptr(cs.rowptr), N.ptr(cs.col),
                                             A.n_users, j0, N.ptr(self.cur),
                                             N.stream_handle(self.dev)), "lg_spread_tile_seek")
         self._seek_at = j0
@@ -1114,7 +1132,7 @@ class TileWeights:
         """Build the tile [j0, min(j0 + tile, stop)); tiles come in ascending order from 0
         (or from the item given to seek()). Builds the group starting at j0 unless j0 is the
         next tile of the group already built."""
-        I = self.A.n_items
+        I = self.n_cols  # (the column count: the catalog's, or the column view's)
         stop = I if stop is None else min(int(stop), I)
         g = self._grp
         if (g is not None and self._seek_at is None and self.j0 is not None
@@ -1124,7 +1142,7 @@ class TileWeights:
         if self._seek_at is not None and j0 == self._seek_at:
             pass  # cursors placed by seek()
         elif j0 == 0:
-            self.cur.copy_(self.A.by_user.rowptr[:-1])
+            self.cur.copy_(self.col_sets.rowptr[:-1])
         elif self.j0 is None or j0 != self.j0 + self.width:
             raise ValueError("tiles must be built in ascending order")
         else:
@@ -1139,11 +1157,12 @@ class TileWeights:
 
     def _build_group(self, j0: int, stop: int, widths: list) -> None:
         A, I, L = self.A, self.A.n_items, N.lib()
+        cs = self.col_sets  # (j0, stop and the tiles are column positions; I counts rows)
         strm = N.stream_handle(self.dev)
         nt = len(widths)
         # group: cursors, bounds, run units and their inclusive scan all on the device; one
         # event wait for the tiles' unit totals (to size ovf), then the rows
-        N.check(L.lg_spread_group_cursor(N.ptr(A.by_user.rowptr), N.ptr(A.by_user.col),
+        N.check(L.lg_spread_group_cursor(N.ptr(cs.rowptr), N.ptr(cs.col),
                                          N.ptr(self.user_cls), A.n_users, j0, self.tile, nt,
                                          stop, N.ptr(self.cur), N.ptr(self.end),
                                          N.ptr(self.counts), N.ptr(self.rec), strm),
@@ -1178,7 +1197,7 @@ class TileWeights:
                              "smaller tile or group)")
         self._grow_ovf(ends[-1])
         N.check(L.lg_spread_group_rows_f64(
-            N.ptr(A.by_item.rowptr), N.ptr(A.by_item.col), N.ptr(A.by_user.col),
+            N.ptr(A.by_item.rowptr), N.ptr(A.by_item.col), N.ptr(cs.col),
             N.ptr(self.inv_deg), I, N.ptr(self.cur), N.ptr(self.counts), N.ptr(self.rec),
             j0, self.tile, nt, stop, N.ptr(self.g_bound), self.vthr,
             N.ptr(self.g_incl), N.ptr(self.g_lines), N.ptr(self.g_ovf),
@@ -1217,7 +1236,7 @@ class TileWeights:
 def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
                       drop: bool = True, eu: torch.Tensor | None = None,
                       ei: torch.Tensor | None = None, users=None,
-                      tile: int = 2048, items: slice | None = None,
+                      tile: int = 2048, items=None,
                       stats: dict | None = None, count_paths: bool = False,
                       col_bounds: bool = True, **_):
     """Per-user top-k of (G *) F, F = A @ HybridS(A, general_W, lam), over item tiles:
@@ -1232,9 +1251,18 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     columns, so only those whose bound times F can beat the list's k-th value get the exact
     fp32 score chain. ``users`` restricts the output to a row range (slice) or to any user ids
     (tensor / list, any order, duplicates allowed: the walk then runs on the taken user-side
-    rows, bitwise the all-users rows); ``items`` restricts the
+    rows, bitwise the all-users rows); ``items`` as a slice restricts the
     candidates to an item range (the lists of disjoint item ranges merge, with
-    merge_topk_lists, into the full lists: the multi-GPU item shard). (The two-kernel form
+    merge_topk_lists, into the full lists: the multi-GPU item shard). Any other ``items``
+    (ids, a bool mask, an ascending device tensor: item_candidates) is a candidate set C: the
+    same kernels walk a column view of general_W (TileWeights / TileWalk ``cols``: the
+    user -> column CSR restricted to C, rb[C], ei[C], the exclusions restricted to C),
+    ceil(|C| / tile) tiles instead of ceil(I / tile), while the rows -- every path
+    u -> i -> v -> j with the full degrees -- stay the whole graph's; the lists hold item
+    ids. Which rows of a tile are merged (V) rows depends on the pairs behind them in that
+    tile, so a candidate tile may sum a column in another order than the full walk: values
+    within 1e-12 relative of the dense path, as without ``items``, and bitwise the
+    no-``items`` call only for C = every item. (The two-kernel form
     -- F written per tile, then a top-K merge -- is a test reference, tests/_ref_paths.py.)
     ``stats`` (optional dict) receives the HIP-event times of the tile
     builds / score bounds / walk launches (t_*_ms, walk_launches) and the walk's (user, item)
@@ -1266,15 +1294,20 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
         u0, u1 = 0, int(ids.numel())
     else:
         u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
-    i0, i1 = (0, A.n_items) if items is None else (max(0, items.start),
-                                                   min(A.n_items, items.stop))
+    cand = None  # a candidate set: the walk's columns are then positions [0, |C|) in it
+    if items is None or isinstance(items, slice):
+        i0, i1 = (0, A.n_items) if items is None else (max(0, items.start),
+                                                       min(A.n_items, items.stop))
+    else:
+        cand = item_candidates(items, A.n_items, dev)
+        i0, i1 = 0, int(cand.numel())
     n = u1 - u0
     vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
     if n == 0 or i1 <= i0:
         return vals, idxs
     tile = min(int(tile), i1 - i0, 4096 if eu is not None else 8192)  # G: <= 64 chunk bounds
-    tw = TileWeights(A, lam, tile)
+    tw = TileWeights(A, lam, tile, cols=cand)
     if i0:
         tw.seek(i0)
     rows = src = None
@@ -1291,7 +1324,7 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     if stats is not None and count_paths:
         _count_rows(tw, A, u0, u1)
     walk = TileWalk(A, u0, u1, i0, k, ex if drop else None, eu_r, ei, tile, col_bounds,
-                    rows=rows, edge_src=src)
+                    rows=rows, edge_src=src, cols=cand)
     evs = [] if stats is not None else None
     for j0 in range(i0, i1, tile):
         if evs is not None:  # per-tile HIP events on the launch stream: build / bounds / walk
@@ -1308,7 +1341,7 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
             e[3].record()
             evs.append(e)
     vals.copy_(walk.vals)
-    idxs.copy_(walk.idxs)
+    idxs.copy_(walk.item_ids())
     if evs:
         torch.cuda.synchronize(dev)
         stats["t_build_ms"] = stats.get("t_build_ms", 0.0) + sum(e[0].elapsed_time(e[1]) for e in evs)
@@ -1337,8 +1370,12 @@ def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets
                               items: slice | None, stats: dict | None, count_paths: bool,
                               col_bounds: bool):
     """spread_topk_tiled for PEEL_K < k <= 1024 (see there): passes of <= PEEL_K entries, each
-    excluding what the earlier ones found."""
+    excluding what the earlier ones found. A candidate set peels in item-id space: every pass
+    gets the same candidates, the ids found are item ids and join the exclusions as such, and
+    each pass restricts them to the candidates' positions itself."""
     dev = A.k_item.device
+    if items is not None and not isinstance(items, slice):
+        items = item_candidates(items, A.n_items, dev)  # (once: a device tensor passes as is)
     ids = None if users is None or isinstance(users, slice) else _user_ids(users, A.n_users, dev)
     if ids is not None:
         users, u0, u1 = ids, 0, int(ids.numel())
@@ -1446,11 +1483,24 @@ class TileWalk:
     (lg_spread_tile_resource_topk_f64 per tile, with lg_score_chunk_bound screening when
     there is a G factor). Holds the running lists (vals fp64 / idxs int64 [n, k]), the
     per-user exclusion cursors and the bf16 score operands, so several walks (a lambda sweep)
-    can share them."""
+    can share them.
+
+    ``cols`` (the column view of TileWeights(cols=...)): the walk's columns are positions in
+    cols. Everything the walk indexes by column -- the exclusions and their cursors, ei and
+    its bf16 bound operands -- is taken for those items here (ex.restrict_cols(cols),
+    ei[cols]); the user side (A.by_user or ``rows``, ra_edge, the row count A.n_items) stays
+    the full graph's. ``idxs`` then holds positions; item_ids() maps them back."""
 
     def __init__(self, A: Interactions, u0: int, u1: int, i0: int, k: int,
                  ex: RowSets | None, eu=None, ei=None, tile: int = 2048,
-                 col_bounds: bool = True, rows: RowSets | None = None, edge_src=None):
+                 col_bounds: bool = True, rows: RowSets | None = None, edge_src=None,
+                 cols: torch.Tensor | None = None):
+        self.cols = cols
+        if cols is not None:
+            ex = ex.restrict_cols(cols) if ex is not None else None
+            if ex is not None and ex.col.numel() == 0:
+                ex = None  # (no excluded candidate at all: an empty tensor has no pointer)
+            ei = ei[cols.to(torch.int64)] if ei is not None else None
         self.A, self.u0, self.u1, self.i0, self.k, self.ex = A, u0, u1, i0, int(k), ex
         # the walk keeps its stream positions in 32 bits
         if A.by_user.col.numel() >= 2**31 or (ex is not None and ex.col.numel() >= 2**31):
@@ -1498,6 +1548,14 @@ class TileWalk:
                                                 self.n, self.i0, N.ptr(self.ex_cur),
                                                 N.stream_handle(self.dev)),
                     "lg_spread_tile_seek")
+
+    def item_ids(self) -> torch.Tensor:
+        """The lists' items as item ids: idxs itself, or mapped through the column view (-1
+        stays -1)."""
+        if self.cols is None:
+            return self.idxs
+        c64 = self.cols.to(torch.int64)
+        return torch.where(self.idxs >= 0, c64[self.idxs.clamp(min=0)], self.idxs)
 
     def bounds(self, j0: int, width: int, scale: "HybridScale | None" = None):
         """(gb, q) score bounds of tile [j0, j0 + width) (q None: chunk bounds only)."""
@@ -1553,7 +1611,8 @@ def spread_lambda_sweep(A: Interactions, lams, k: int, excl: RowSets | None,
              bounds of every tile would not fit). If the cache does not fit, each lambda
              rebuilds the tiles. At k > 128 the tiled route calls spread_topk_tiled per
              lambda (its peeled passes; no shared TileWalk, no tile cache).
-    Every result is bitwise the one spread_recommend(A, lam, ...) returns."""
+    Every result is bitwise the one spread_recommend(A, lam, ...) returns. The sweep ranks the
+    whole catalog: it takes no items= (spread_recommend's candidate set) yet."""
     lams = [float(x) for x in lams]
     k = int(k)
     dev = A.k_item.device
@@ -1635,7 +1694,8 @@ def dense_spread_fits(n_items: int, device, fraction: float = 0.25) -> bool:
 def spread_recommend(A: Interactions, lam: float, k: int, excl: RowSets | None,
                      drop: bool = True, eu: torch.Tensor | None = None,
                      ei: torch.Tensor | None = None, transpose: bool = False,
-                     tiled: bool | None = None, users=None, tile: int | None = None):
+                     tiled: bool | None = None, users=None, tile: int | None = None,
+                     items=None, W: torch.Tensor | None = None):
     """Per-user top-k of (G *) A @ HybridS(A, general_W(^T), lam), dense (I x I matrices on
     the device) or factored over item tiles (tiled=None: dense when it fits). The two
     paths give the same values within a few ulp (the factored walk sums each column's paths
@@ -1648,14 +1708,48 @@ def spread_recommend(A: Interactions, lam: float, k: int, excl: RowSets | None,
     result to those users: row j is bitwise row users[j] of the all-users call on the same
     path. The user side (interaction rows, exclusion rows, eu rows) is taken for those ids;
     the item side (W, or the general_W tiles) comes from the full A. ``tile`` is the tiled
-    path's tile width (default: spread_topk_tiled's)."""
+    path's tile width (default: spread_topk_tiled's).
+
+    ``items`` (item_candidates' forms: ids, a bool mask, or a strictly ascending device
+    tensor) restricts the ranking to a candidate item set C -- the in-stock items, one
+    category, a retrieval stage's output. Only the ranked columns are restricted: the paths
+    u -> i -> v -> j run over every item i and user v of the full graph with the full
+    degrees, F_C[u, p] = sum_{i in items(u)} W[i, C[p]] with W built from the whole A. Row u
+    is the first k of {(v(u, j), j) : j in C, j not dropped by u's exclusions} under (value
+    desc, item id asc), real item ids, NaN and -inf never rank, short rows padded {-inf, -1};
+    drop=False keeps excluded candidates. Dense: lg_spread_rows_topk_items_f64 (csrc/
+    rows_topk_items.hip, any k <= 1024, all users or ``users``), or, where
+    _spread_items_route measured it slower, the existing kernels and an F[:, C] gather --
+    the same bits, and bit for bit rows_topk(spread_resource(A, W)[:, C], k,
+    excl.restrict_cols(C), drop, eu, ei[C]) mapped back through C. Tiled: the column view of
+    spread_topk_tiled (values within 1e-12 relative of the dense path).
+
+    ``W``: a prebuilt spread_hybrid(A, lam) for the dense path (a per-request caller must not
+    rebuild an I x I matrix per call; ``lam`` is then not read). With tiled=True it raises."""
     if tiled is None:
-        tiled = not dense_spread_fits(A.n_items, A.k_item.device)
+        tiled = W is None and not dense_spread_fits(A.n_items, A.k_item.device)
     if tiled:
+        if W is not None:
+            raise ValueError("spread_recommend: W= is the dense path's matrix; the tiled path "
+                             "never holds one (tiled=True with W)")
         kw = {} if tile is None else {"tile": int(tile)}
+        if items is not None:
+            if isinstance(items, slice):
+                raise ValueError("spread_recommend: items= is a candidate set (ids or a mask); "
+                                 "item ranges are spread_topk_tiled's shards")
+            kw["items"] = items
         return spread_topk_tiled(A, lam, k, excl, drop, eu, ei, users=users, **kw)
     ids = None if users is None else _user_ids(users, A.n_users, A.k_item.device)
-    W = spread_hybrid(A, lam)  # (= hybrid_weight(spread_general(A), ..., transpose))
+    if W is None:
+        W = spread_hybrid(A, lam)  # (= hybrid_weight(spread_general(A), ..., transpose))
+    elif W.shape != (A.n_items, A.n_items) or W.dtype != torch.float64:
+        raise ValueError(f"W of shape {tuple(W.shape)} / {W.dtype}, expected the fp64 "
+                         f"({A.n_items}, {A.n_items}) matrix of spread_hybrid")
+    if items is not None:
+        if isinstance(items, slice):
+            raise ValueError("spread_recommend: items= is a candidate set (ids or a mask)")
+        cand = item_candidates(items, A.n_items, A.k_item.device)
+        return _spread_topk_items(A, W, ids, cand, k, excl, drop, eu, ei)
     if ids is not None:
         return _spread_topk_users(A, W, ids, k, excl, drop, eu, ei)
     return spread_topk(A, W, k, excl, drop, eu, ei)
@@ -1685,4 +1779,128 @@ def _spread_topk_users(A: Interactions, W: torch.Tensor, ids: torch.Tensor, k: i
         v, i = rows_topk(Fb, k, ex.slice_rows(b0, b1) if ex is not None else None, drop,
                          None if eu_r is None else eu_r[b0:b1], ei)
         vals[b0:b1], idxs[b0:b1] = v, i
+    return vals, idxs
+
+
+# ------------------------------------------------ dense spreading over a candidate item set
+# rows of at least this many candidates get several waves each in lg_spread_rows_topk_items_f64
+# (kSplitCand, csrc/rows_topk_items.hip), shorter ones one
+ROWS_ITEMS_SPLIT = 512
+
+
+def spread_rows_topk_items(rows: RowSets, W: torch.Tensor, cand: torch.Tensor, k: int,
+                           excl: RowSets | None = None, drop: bool = True,
+                           eu: torch.Tensor | None = None, ei: torch.Tensor | None = None):
+    """lg_spread_rows_topk_items_f64: per row r of ``rows`` (interaction rows: A.by_user, or
+    taken rows of it) the top-k of (G *) sum_{i in rows[r]} W[i, j] over the candidates j in
+    ``cand`` (item_candidates' int32 tensor: strictly ascending ids), excluded items (``excl``:
+    item-id columns, rows aligned with ``rows``) dropped or kept. W: the full fp64 [I, I]
+    matrix; eu: the rows' embeddings, ei: the full item table. Returns (values fp64 [n, k],
+    item ids int64 [n, k], {-inf, -1} padding). k in [1, 1024]; nothing is gathered."""
+    k = int(k)
+    if k < 1 or k > 1024:
+        raise ValueError(f"k={k} not in [1, 1024]")
+    N.require_gpu(W, "W")
+    I = rows.n_cols
+    if W.dtype != torch.float64 or W.dim() != 2 or W.shape != (I, I):
+        raise ValueError(f"W must be the float64 ({I}, {I}) matrix, got {tuple(W.shape)} "
+                         f"{W.dtype}")
+    W = W.contiguous()
+    dev = W.device
+    if cand.dtype != torch.int32 or cand.device != dev:
+        raise ValueError("cand must be item_candidates' int32 tensor on W's device")
+    cand = cand.contiguous()
+    n, nc = rows.n_rows, int(cand.numel())
+    # (an empty tensor has no pointer to pass and the entry refuses NULL: a one-element stand-in
+    # that is never read -- the entry pads every row on n_cand = 0, rows without items sum to 0)
+    cand_p = cand if nc else torch.zeros(1, dtype=torch.int32, device=dev)
+    col_p = rows.col if rows.col.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
+    if excl is not None and excl.n_rows != n:
+        raise ValueError(f"exclusion rows {excl.n_rows} != rows {n}")
+    if excl is not None and excl.col.numel() == 0:
+        excl = None  # (an empty tensor has no pointer to pass)
+    d = 0
+    if eu is not None:
+        eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+        d = eu.shape[1]
+        if eu.shape[0] != n or ei.shape != (I, d):
+            raise ValueError("eu: one row per row of `rows`; ei: the full item table")
+    val = torch.empty((n, k), dtype=torch.float64, device=dev)
+    idx = torch.empty((n, k), dtype=torch.int64, device=dev)
+    N.check(N.lib().lg_spread_rows_topk_items_f64(
+        N.ptr(rows.rowptr), N.ptr(col_p), N.ptr(W), n, I, N.ptr(cand_p), nc, N.ptr(eu),
+        N.ptr(ei), d, N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+        N.LG_EXCL_DROP if drop else N.LG_EXCL_NONE, k, N.ptr(val), N.ptr(idx),
+        N.stream_handle(dev)), "lg_spread_rows_topk_items_f64")
+    return val, idx
+
+
+# spread_recommend(items=...) on the dense path sends a request to the fused kernel
+# (lg_spread_rows_topk_items_f64) or to the existing pair -- lg_spread_resource_f64, an F[:, C]
+# gather, rows_topk, the id map -- whichever profiles/spread_items.json
+# (scripts/spread_items_time.py: 600 x 20,000, d = 64, with and without G, users 1 / 8 / 16 /
+# 600, share 1.0 / 0.5 / 0.1 / 0.01, k 20 / 100 / 256) measured faster by more than the larger
+# of the two spreads. There the fused kernel wins every k, with and without G, for all 600 users
+# at a candidate share <= 0.1 (0.61-0.72 of gather's time at 0.1, 0.12-0.14 at 0.01); at share
+# 0.5 it wins without G only (0.82-0.91; with G 0.91-0.94, inside the spread at k <= 100) and
+# at 1.0 it loses with G (1.07-1.34). For 1 / 8 / 16 users both routes are 0.35-1.1 ms of
+# mostly host work (the row takes, the launches): the fused median is 0.72-0.98 of gather's at
+# share <= 0.1 and 1.02-1.47 above, never beyond the 0.2-0.7 spreads of such calls -- no win
+# is established, so they stay on the existing kernels. Between 16 and 600 users nothing was
+# timed: the bound is the smallest user count at which the win was measured.
+SPREAD_ITEMS_FUSED_MIN_USERS = 600
+SPREAD_ITEMS_FUSED_MAX_SHARE = 0.1
+
+
+def _spread_items_route(n_rows: int, n_cand: int, n_items: int) -> str:
+    """"fused" or "gather" (see SPREAD_ITEMS_FUSED_*); both give the same bits."""
+    if n_rows >= SPREAD_ITEMS_FUSED_MIN_USERS and \
+            n_cand <= SPREAD_ITEMS_FUSED_MAX_SHARE * n_items:
+        return "fused"
+    return "gather"
+
+
+def _spread_topk_items(A: Interactions, W: torch.Tensor, ids, cand: torch.Tensor, k: int,
+                       excl: RowSets | None, drop: bool, eu, ei, route: str | None = None):
+    """spread_recommend's dense path over the candidates ``cand`` for all users (ids None)
+    or the users ``ids`` (interaction, exclusion and eu rows taken as _spread_topk_users
+    does). route: "fused" (lg_spread_rows_topk_items_f64), "gather" (lg_spread_resource_f64
+    block by block, F[:, cand], rows_topk on the renumbered exclusions and ei[cand], ids
+    mapped back) or None: _spread_items_route. Bitwise the same lists either way."""
+    I = A.n_items
+    rows = A.by_user if ids is None else A.by_user.take(ids)
+    ex = excl if ids is None or excl is None else excl.take(ids)
+    eu_r = eu if ids is None or eu is None else eu[ids]
+    n, nc = rows.n_rows, int(cand.numel())
+    if route is None:
+        route = _spread_items_route(n, nc, I)
+    if route == "fused":
+        return spread_rows_topk_items(rows, W, cand, k, ex, drop, eu_r, ei)
+    if route != "gather":
+        raise ValueError(f"route {route!r} not in ('fused', 'gather')")
+    k = int(k)
+    W = W.contiguous()
+    dev = W.device
+    vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
+    idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    if n == 0 or nc == 0:
+        if k < 1 or k > 1024:
+            raise ValueError(f"k={k} not in [1, 1024]")
+        return vals, idxs
+    c64 = cand.to(torch.int64)
+    exc = ex.restrict_cols(cand) if ex is not None else None
+    if exc is not None and exc.col.numel() == 0:
+        exc = None  # (no excluded candidate at all: an empty tensor has no pointer to pass)
+    eic = None if ei is None else ei[c64]
+    block = max(1, min(n, (1 << 30) // max(1, I * 8)))  # ~1 GiB of F per block
+    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=dev)
+    for b0 in range(0, n, block):
+        b1 = min(n, b0 + block)
+        Fb = buf[: b1 - b0]
+        N.check(N.lib().lg_spread_resource_f64(
+            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
+            Fb.stride(0), N.stream_handle(dev)), "lg_spread_resource_f64")
+        v, i = rows_topk(Fb[:, c64], k, exc.slice_rows(b0, b1) if exc is not None else None,
+                         drop, None if eu_r is None else eu_r[b0:b1], eic)
+        vals[b0:b1], idxs[b0:b1] = v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
     return vals, idxs

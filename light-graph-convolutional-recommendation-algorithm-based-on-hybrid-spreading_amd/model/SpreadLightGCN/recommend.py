@@ -41,11 +41,13 @@ def recommendForAllUser(F_new: np.ndarray, user_num: int, train_data_df: pd.Data
 
 def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.DataFrame,
                          val_data_df: pd.DataFrame, lambda_val: float, k: int, device=None,
-                         tiled: bool | None = None, users=None):
+                         tiled: bool | None = None, users=None, items=None):
     """Device (values fp64, items int64) of the whole LGCNHS recommendation. k in [1, 1024];
     above 128 the dense path takes lg_rows_topk_wide_f64 and the tiled path peels
     ceil(k / 128) walks (ops.spread_topk_tiled). ``users`` (ids, tensor or list): only those
-    users' rows, in that order (ops.spread_recommend)."""
+    users' rows, in that order (ops.spread_recommend). ``items`` (ids, a bool mask or an
+    ascending device tensor: ops.item_candidates): rank only those items -- the spreading and
+    the embeddings stay the whole graph's -- with real item ids in the lists."""
     dev = device or gpu_device(model.users_emb.weight)
     both = pd.concat([train_data_df, val_data_df])
     inter = ops.Interactions.from_pairs(
@@ -55,7 +57,7 @@ def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.
     ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
     # dense I x I general_W / W when they fit, else the factored tile path (same values within a few ulp)
     return ops.spread_recommend(inter, lambda_val, k, inter.by_user, drop=True, eu=eu, ei=ei,
-                                tiled=tiled, users=users)
+                                tiled=tiled, users=users, items=items)
 
 
 def recommendSpreadLightGCN(user_num: int, item_num: int, rating_df: pd.DataFrame,

@@ -48,11 +48,13 @@ def recommendForAllUser(F_new: np.ndarray, user_num: int, train_data_df: pd.Data
 def spread_method_topk(user_num: int, item_num: int, train_data_df: pd.DataFrame,
                        val_data_df: pd.DataFrame, method: str, lambda_val: float,
                        dataset: str, k: int, unfiltered: bool = False, device=None,
-                       tiled: bool | None = None, users=None):
+                       tiled: bool | None = None, users=None, items=None):
     """Device (values, items) of the whole spreading recommendation. k in [1, 1024]; above
     128 the dense path takes lg_rows_topk_wide_f64 and the tiled path peels ceil(k / 128)
     walks (ops.spread_topk_tiled). ``users`` (ids, tensor or list): only those users' rows,
-    in that order (ops.spread_recommend)."""
+    in that order (ops.spread_recommend). ``items`` (ids, a bool mask or an ascending device
+    tensor: ops.item_candidates): rank only those items -- the spreading still runs over the
+    whole graph -- with real item ids in the lists (ops.spread_recommend)."""
     dev = device or gpu_device()
     both = pd.concat([train_data_df, val_data_df])
     inter = ops.Interactions.from_pairs(
@@ -66,7 +68,8 @@ def spread_method_topk(user_num: int, item_num: int, train_data_df: pd.DataFrame
     excl = inter.by_user  # train|val positives == the nonzeros of A
     # dense I x I general_W / W when they fit, else the factored tile path (same values within a few ulp)
     return ops.spread_recommend(inter, lambda_val, k, excl, drop=not unfiltered,
-                                transpose=transpose, tiled=tiled, users=users)
+                                transpose=transpose, tiled=tiled, users=users,
+                                items=items)
 
 
 def recommendSpreadMethod(user_num: int, item_num: int, train_data_df: pd.DataFrame,
