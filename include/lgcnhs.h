@@ -206,8 +206,8 @@ int lg_score_topk_f32(const float *eu, const float *ei, int64_t n_users, int64_t
                       float mask_value, int32_t k, int32_t n_splits, float *out_val,
                       int64_t *out_idx, void *ws, size_t ws_bytes, lg_stream_t stream);
 
-/* lg_score_topk_f32 with a bf16 MFMA screen (csrc/topk.hip K2r): the same outputs bit
- * for bit (values, ids, order). eu_bf16 / ei_bf16: lg_bound_prep_f32's bf16 copies of eu / ei
+/* lg_score_topk_f32 (csrc/topk_plain.hip) with a bf16 MFMA screen (csrc/topk.hip K2r): the
+ * same outputs bit for bit (values, ids, order). eu_bf16 / ei_bf16: lg_bound_prep_f32's bf16 copies of eu / ei
  * (16-byte aligned). umarg[u] (fp32, per user) must bound |bf16 MFMA product - fp32 chain|
  * over every item, with slack for the fp32 roundings of the screen's own compares:
  *   umarg[u] >= (||du|| I + (||eu[u]|| + ||du||) DI + (2.01 dim 2^-24 + 2^-22) ||eu[u]|| I)

@@ -15,9 +15,6 @@ namespace lg {
 constexpr int kMaxBlocks = 512;  // workgroups of the scoring grid: partial lists per user
 constexpr int kMergeWaves = 16;  // waves of k_topk_batch_merge's workgroup (one per user)
 
-// list capacity CAP = 64 M entries per (wave, user): 2k <= CAP for the pairwise merges
-inline int list_cap_m(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }
-
 // Merge the n_lists partial lists of each of n_batch users (part_val / part_idx: list r of
 // user b at ((r n_batch + b) k), sorted, padded with id -1) into out_val / out_idx.
 int launch_batch_merge(const float *part_val, const int32_t *part_idx, int n_batch, int k,

@@ -21,7 +21,7 @@
 
 namespace lg {
 
-// fp32 score in the chain order of lg_score_topk_f32 (see topk.hip header).
+// fp32 score in the chain order of lg_score_topk_f32 (see topk_plain.hip header).
 template <int D>
 __device__ __forceinline__ float chain_score(const float *__restrict__ us,
                                              const float *__restrict__ it) {

@@ -1,11 +1,12 @@
 // The shared pieces of the K2 stream -- score a range of items against a wave's users, 16
-// items per step, and keep each user's best k -- for k_score_topk and k_topk_ring (topk.hip),
-// k_score_topk_wide (topk_wide.hip) and k_score_topk_batch (topk_batch.hip):
+// items per step, and keep each user's best k -- for k_score_topk (topk_plain.hip), k_topk_ring
+// (topk.hip), k_score_topk_wide (topk_wide.hip) and k_score_topk_batch (topk_batch.hip):
 //
 //   load_piece, load_item_tile  the MFMA operand loads
 //   max4, above, entry_thr      the one-max-one-compare filter and the admission threshold
 //   mask_excluded_run           the lazy exclusion of a list's new entries, for lists in LDS
-//   split_len                   the split arithmetic of the launchers
+//   split_len, screened_splits, list_cap_m, launch_topk_merge
+//                               the split and list arithmetic of the launchers; the split merge
 //
 // Each kernel keeps its own text of the software pipeline (the loop of k_score_topk, described
 // there): written once over a list policy, hipcc allocated more registers in some
@@ -78,6 +79,24 @@ inline int64_t split_len(int64_t n_items, int n_splits) {
   per = (per + 15) / 16 * 16;
   return per < 16 ? 16 : per;
 }
+
+// the screened kernel's splits: at least one per 2^20 items (k_topk_ring's 16-bit tile
+// indices); split_len of it is then <= 2^20 (a multiple of 16)
+constexpr int kTileBits = 16;  // tile index field: splits of at most 2^20 items
+inline int screened_splits(int64_t n_items, int n_splits) {
+  const int64_t need = (n_items + ((int64_t)1 << (kTileBits + 4)) - 1) >> (kTileBits + 4);
+  return n_splits > need ? n_splits : (int)need;
+}
+
+// list capacity CAP = 64 M entries per (wave, user) at this k (2k <= CAP for the pairwise merges
+// of K2b and K2i)
+inline int list_cap_m(int k) { return k <= 32 ? 1 : (k <= 64 ? 2 : 4); }
+
+// Merge the n_splits partial lists of each user (k_topk_merge; <2> for k <= 64, else <4>; four
+// users per block) for lg_score_topk_f32 and lg_score_topk_screened_f32: defined once, in
+// topk_plain.hip.
+void launch_topk_merge(const float *part_val, const int32_t *part_idx, int64_t n_users, int k,
+                       int n_splits, float *out_val, int64_t *out_idx, hipStream_t stream);
 
 // Exclusion is applied lazily: a candidate enters on its raw score (or on the mask value when
 // that alone beats tau), and the entries [c0, n) added since the user's last compaction are

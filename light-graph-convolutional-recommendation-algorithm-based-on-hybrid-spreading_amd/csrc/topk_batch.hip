@@ -2,7 +2,7 @@
 // into the full tables), gfx950 f32 MFMA.
 //
 // The request form of model/LightGCN/recommend.py:83-114: the same score, mask and top-k as
-// K2 (csrc/topk.hip), for the rows user_ids[0 .. n_batch) of users_emb only. Row b of the
+// K2 (csrc/topk_plain.hip), for the rows user_ids[0 .. n_batch) of users_emb only. Row b of the
 // output is lg_score_topk_f32's row user_ids[b] bit for bit: the score is k_score_topk's
 // chain (v_mfma_f32_16x16x4_f32, D/4 dependent steps from a zero accumulator, lane l = item
 // row l & 15 as A, user column l & 15 as B, k-slot l >> 4), admission is strict (NaN and -inf

@@ -1,5 +1,5 @@
 // K2w: full-catalog scoring + exclusion mask + streaming top-K for every k <= 1024, gfx950
-// f32 MFMA. The wide twin of K2 (csrc/topk.hip, k <= 128).
+// f32 MFMA. The wide twin of K2 (csrc/topk_plain.hip, k <= 128).
 //
 // Replaces model/LightGCN/recommend.py:83-114 (identical in LightGCNOpti/recommend.py and
 // LightGCN/evaluation.py:31-51) for any RECOMMEND["k"] up to 1024:
@@ -8,7 +8,7 @@
 //     _, recommendations = torch.topk(score, k)
 //
 // The score, the software pipeline, the one-max-one-compare filter and the admission rule are
-// k_score_topk's (see the head of topk.hip; the loads, the filter, the threshold rule and the
+// k_score_topk's (see the head of topk_plain.hip; the loads, the filter, the threshold rule and the
 // lazy exclusion are the one text of score_stream.h): 16 users per wave as MFMA B fragments,
 // 16-item tiles as A fragments through raw buffer loads, the v_mfma_f32_16x16x4_f32 chain
 //     acc = 0; for s < Q: for g < 4: acc = fmaf(u[g*Q+s], i[g*Q+s], acc),

@@ -373,8 +373,8 @@ def _wide_resident_blocks(device, k: int, d: int = 64) -> int:
 
 
 def _users_per_block(k: int, screen: bool = False, d: int = 64) -> int:
-    """Users per workgroup of csrc/topk.hip's launches (dispatch_topk / _screen) and, for
-    k > 128, of csrc/topk_wide.hip's (4 waves x 16 users)."""
+    """Users per workgroup of the launches of csrc/topk_plain.hip (dispatch_topk) and
+    csrc/topk.hip (dispatch_topk_screen) and, for k > 128, of csrc/topk_wide.hip's (4 waves x 16 users)."""
     if k > 128:
         return 64
     if screen:  # (8 waves x 2 groups; k > 64 at d <= 64: 1 group, LG_GL4_NG)

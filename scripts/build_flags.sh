@@ -1,7 +1,8 @@
 #!/bin/bash
 # Measurement builds: liblgcnhs.so with one csrc source compiled with extra flags:
 #   scripts/build_flags.sh NAME "FLAGS" [SRC]  ->  lib/ab/liblgcnhs_NAME.so
-# (e.g. the ring shape of csrc/topk.hip: "-DLG_RING_NBUF=9 -DLG_RING_LA=5 -DLG_RING_LAG=2").
+# (e.g. the ring shape of csrc/topk.hip: "-DLG_RING_NBUF=9 -DLG_RING_LA=5 -DLG_RING_LAG=2";
+# SRC defaults to topk, the screened ring; the plain kernel's -DLG_TOPK_PROBE takes SRC = topk_plain).
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/light-graph-convolutional-recommendation-algorithm-based-on-hybrid-spreading_amd/csrc

@@ -1,7 +1,8 @@
 """Summarise scripts/gpu_topk_pmc.sh (rocprofv3 kernel trace + PMC passes over the screened
 top-K at C5: 32768 users x 1M items, k = 20 (or K), d = 64 and 128) into
-profiles/pmc_topk.json, keyed "c5-d<D>/topk" (k = 20) or "c5-d<D>/topk_k<K>", with the hash of csrc/topk.hip (bench.py uses a record only for the
-source it was measured on).
+profiles/pmc_topk.json, keyed "c5-d<D>/topk" (k = 20) or "c5-d<D>/topk_k<K>", with the hash of csrc/topk.hip -- the file
+that holds the screened ring and nothing else (bench.py uses a record only for the source it was
+measured on).
 
 The kernel is k_topk_ring<D, NG, WAVES, M, CAP, NBUF, LA, LAG, SEEDP> (csrc/topk.hip K2r): for
 k <= 32 a seed pass (SEEDP = true, the first 1/16 of the items), then the main pass. Per call: the

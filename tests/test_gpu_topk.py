@@ -70,6 +70,41 @@ def test_score_topk_bit_exact(d, k, screen):
         assert np.array_equal(v.cpu().numpy().view(np.uint32), ov.view(np.uint32))
 
 
+_SPLIT_MERGE = {}  # (I, k) -> the oracle's lists of the 5 users, computed once
+
+
+def _split_merge_case(I, k):
+    """5 users x I items, d = 32; every user's exclusion row straddles each split end of the
+    2-, 3- (600 items: 304; 208, 416) and 3-way (300 items: 112, 224) splits."""
+    if (I, k) not in _SPLIT_MERGE:
+        eu, ei = _emb(5, 32, 61), _emb(I, 32, 62)
+        ends = [e for e in (112, 208, 224, 304, 416) if e + 2 <= I]
+        its = np.array([e + o for e in ends for o in (-2, -1, 0, 1)])
+        rp, col = O.exclusion_csr(5, I, (np.repeat(np.arange(5), its.size), np.tile(its, 5)))
+        ov, oi = O.chain_topk(eu.numpy(), ei.numpy(), rp, col, k)
+        _SPLIT_MERGE[(I, k)] = (eu, ei, rp, col, ov, oi)
+    return _SPLIT_MERGE[(I, k)]
+
+
+@pytest.mark.parametrize("screen", [True, False])
+@pytest.mark.parametrize("U", [1, 5])
+def test_split_merge_from_both_entries(U, screen):
+    """lg_score_topk_f32 and lg_score_topk_screened_f32 both merge their splits' partial lists
+    with k_topk_merge through the one launch_topk_merge: 1 and 5 users (no multiple of the merge
+    block's 4: waves leave at user >= n_users), 2 and 3 splits of 600 items at k = 20, 64, 65,
+    128 (k_topk_merge<2> up to 64, <4> above), 3 splits of 300 items at k = 128 (every partial
+    list shorter than k, padded with -1), exclusions on both sides of every split end. Values,
+    ids, order and padding equal the C chain oracle's bit for bit."""
+    from lgcnhs import ops
+    for I, ns, k in [(600, ns, k) for ns in (2, 3) for k in (20, 64, 65, 128)] + [(300, 3, 128)]:
+        eu, ei, rp, col, ov, oi = _split_merge_case(I, k)
+        rpu = rp[:U + 1]
+        ex = _rowsets(rpu, col[:rpu[-1]], U, I)
+        v, i = ops.score_topk(eu[:U].to(DEV), ei.to(DEV), k, ex, n_splits=ns, screen=screen)
+        np.testing.assert_array_equal(i.cpu().numpy(), oi[:U], err_msg=str((I, ns, k)))
+        assert np.array_equal(v.cpu().numpy().view(np.uint32), ov[:U].view(np.uint32)), (I, ns, k)
+
+
 @pytest.mark.parametrize("k", [20, 64, 100, 128])
 def test_screened_topk_near_ties_and_wide_norms(k):
     """The bf16 screen's margin under stress: items that differ below bf16 resolution (their
