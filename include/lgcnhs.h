@@ -308,6 +308,50 @@ int lg_score_topk_batch_items_f32(const float *eu, const float *ei, const int64_
                                   float mask_value, int32_t k, float *out_val, int64_t *out_idx,
                                   void *ws, size_t ws_bytes, lg_stream_t stream);
 
+/* Top-k where every row has its own candidate list (csrc/topk_cand.hip K2c): the request form
+ * of model/LightGCN/recommend.py:83-114 behind a per-user retrieval stage, and the ranking of a
+ * held-out positive among sampled negatives. The candidates are a CSR: cand_rowptr (device,
+ * int64, n_rows + 1), cand_col (device, int32), ids strictly ascending inside a row and in
+ * [0, n_items). Row r is scored for user user_ids[r] (device, int64; NULL: user r). Output row
+ * r is the first k of {(v(u_r, i), i) : i in candidate row r} under (value desc, item id asc),
+ * v the fp32 chain score of lg_score_topk_f32 or mask_value where i is in u_r's row of
+ * ex_rowptr / ex_col (the FULL table's exclusion CSR, indexed by user id); NaN and -inf never
+ * rank; shorter rows are padded with {-inf, -1}; the ids returned are real item ids. That is
+ * lg_score_topk_f32(eu[u_r], ei[cand_r], ...) with the exclusion columns renumbered and the ids
+ * mapped back, bit for bit, without gathering a row. max_len is the caller's bound on the row
+ * length: a row's candidates at positions >= max_len are ignored (defined, not an error). Each
+ * row is scored in n_seg in [1, 4096] segments of split_len(max_len, n_seg) positions (one wave
+ * per segment); the result does not depend on n_seg. n_seg > 1 keeps one partial list per
+ * (segment, row) in the workspace: lg_score_topk_cand_ws_bytes = n_seg x n_rows x k x 8 (0 for
+ * n_seg == 1 and for arguments the call refuses). k in [1, 128], dim in {32, 64, 128},
+ * n_items < 2^31 - 1, max_len in [1, 2^31). Memory-safe on any list: a candidate id outside
+ * [0, n_items) reads row 0 and never ranks, a user id outside [0, n_table_users) gives an
+ * all-padding row, a row that is not ascending gives unspecified lists. */
+size_t lg_score_topk_cand_ws_bytes(int64_t n_rows, int32_t dim, int32_t k, int32_t n_seg);
+/* model/LightGCN/recommend.py:83-114 per row over the row's own candidates (above). LG_ERR_ARG
+ * on a null pointer, n_rows < 1 or n_rows x n_seg / 4 past the grid limit, bad n_items,
+ * max_len, dim, k or n_seg, a half-set exclusion pair; LG_ERR_WORKSPACE when the segments in
+ * use need a workspace and ws is NULL or short; all before any launch. Never allocates, never
+ * syncs. */
+int lg_score_topk_cand_f32(const float *eu, const float *ei, const int64_t *user_ids,
+                           int64_t n_rows, int64_t n_table_users, int64_t n_items,
+                           const int64_t *cand_rowptr, const int32_t *cand_col, int64_t max_len,
+                           int32_t dim, const int64_t *ex_rowptr, const int32_t *ex_col,
+                           float mask_value, int32_t k, int32_t n_seg, float *out_val,
+                           int64_t *out_idx, void *ws, size_t ws_bytes, lg_stream_t stream);
+/* The scores of given (user, item) pairs -- the score[u, i] of model/LightGCN/recommend.py:83-114
+ * read at the candidates only (csrc/topk_cand.hip): lg_score_topk_cand_f32's inputs, gather and
+ * chain with no lists. out (device, fp32, one per entry of cand_col) gets at every position p
+ * the chain score of (u_r, cand_col[p]), r the row of p, or mask_value where the item is in
+ * u_r's exclusion row; -inf at positions >= max_len within their row, for an id outside
+ * [0, n_items) and in the rows of a user id outside the table. Rows need not be ascending.
+ * Refusals as above (no k, n_seg or workspace). Never allocates, never syncs. */
+int lg_score_cand_f32(const float *eu, const float *ei, const int64_t *user_ids, int64_t n_rows,
+                      int64_t n_table_users, int64_t n_items, const int64_t *cand_rowptr,
+                      const int32_t *cand_col, int64_t max_len, int32_t dim,
+                      const int64_t *ex_rowptr, const int32_t *ex_col, float mask_value,
+                      float *out, lg_stream_t stream);
+
 /* Dense masked score matrix G[u][i] (same score definition and mask as above), written
  * with leading dimension ldg. Replaces getAllocateMat's matmul + masks
  * (model/SpreadLightGCN/model.py:74-104, model/SpreadLightGCNOpti/model.py:139-169). */

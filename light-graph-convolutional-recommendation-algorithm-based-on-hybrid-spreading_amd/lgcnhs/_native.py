@@ -97,6 +97,16 @@ SIGNATURES = {
         [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp,
          _sz, _vp],
     ),
+    "lg_score_topk_cand_ws_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "lg_score_topk_cand_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _i32, _i32, _vp,
+         _vp, _vp, _sz, _vp],
+    ),
+    "lg_score_cand_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp],
+    ),
     "lg_score_topk_screened_f32": (
         ctypes.c_int,
         [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp,

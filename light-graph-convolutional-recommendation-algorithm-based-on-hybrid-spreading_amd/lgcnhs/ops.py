@@ -768,6 +768,174 @@ def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
     return _topk_lists("lg_score_topk_batch", BATCH_CALL_USERS, eu, ei, ids, k, excl, mask_value)
 
 
+CAND_K_MAX = 128       # lg_score_topk_cand_f32's largest k (csrc/topk_cand.hip)
+CAND_SEG_MAX = 4096    # ... and its most segments per row
+# cand_segments gives a row no segment shorter than this many candidates. Set from the
+# `min_seg_sweep` of profiles/topk_cand.json (scripts/topk_cand_time.py: K2c at 64 x 10,000 and
+# 16 x 100,000 candidates over 1M items, d in {64, 128}, k in {20, 100}, the plans for 128 ..
+# 4096): 1024 is the fastest or within 5 % of it in all four 64-row cases and within 6-14 % of
+# the fastest (2048) in the four 16-row cases; 256 costs 0.99-1.17x / 1.27-1.52x of 1024's time
+# there, 2048 1.32-1.50x at 64 rows (too few waves), 128 and 4096 lose everywhere. Shorter
+# segments pay a final sort, a partial list and a merge step each.
+CAND_MIN_SEG = 1024
+
+
+def candidate_rows(cands, n_rows: int, n_items: int, device) -> RowSets:
+    """Per-row candidate lists as the kernel takes them: a RowSets of n_rows rows over n_items
+    columns on `device` (rowptr int64, col int32 strictly ascending inside a row).
+
+    cands: a RowSets (taken as it is); a dict {row: ids} (rows that are not keys are empty); a
+    list of n_rows id lists; or a (rows, items) pair of equally long arrays. Host inputs are
+    validated -- ValueError on a non-integer id, an item id outside [0, n_items) or a row
+    outside [0, n_rows) -- then sorted and de-duplicated per row on the host. A pair of device
+    tensors is taken as given: the caller guarantees (row, item) ascending order without
+    duplicates, nothing is checked and nothing syncs (the kernel reads no memory outside the
+    tables on any list; item_candidates' policy)."""
+    n_rows, n_items = int(n_rows), int(n_items)
+    if isinstance(cands, RowSets):
+        if cands.n_rows != n_rows:
+            raise ValueError(f"candidate rows {cands.n_rows} != rows {n_rows}")
+        return cands
+
+    def ints(x, what):
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        if t.numel() and (t.dtype == torch.bool or t.is_floating_point() or t.is_complex()):
+            raise ValueError(f"{what} ids must be integers")
+        return t.reshape(-1)
+
+    if isinstance(cands, dict):
+        keys = list(cands)
+        lists = [ints(cands[r], "item").cpu().to(torch.int64) for r in keys]
+        rows = torch.repeat_interleave(ints(keys, "row").to(torch.int64),
+                                       torch.tensor([int(x.numel()) for x in lists],
+                                                    dtype=torch.int64))
+        items = torch.cat(lists) if lists else torch.zeros(0, dtype=torch.int64)
+    elif isinstance(cands, tuple) and len(cands) == 2:
+        rows, items = ints(cands[0], "row"), ints(cands[1], "item")
+        if rows.numel() != items.numel():
+            raise ValueError(f"{rows.numel()} rows for {items.numel()} items")
+        if rows.is_cuda and items.is_cuda:
+            keys = rows.to(device, torch.int64).contiguous()
+            from .graph import _rowptr_from_sorted
+            return RowSets(_rowptr_from_sorted(keys, n_rows),
+                           items.to(device, torch.int32).contiguous(), n_rows, n_items)
+        rows, items = rows.cpu().to(torch.int64), items.cpu().to(torch.int64)
+    else:
+        lists = [ints(x, "item").cpu().to(torch.int64) for x in cands]
+        if len(lists) != n_rows:
+            raise ValueError(f"{len(lists)} candidate lists for {n_rows} rows")
+        rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64),
+                                       torch.tensor([int(x.numel()) for x in lists],
+                                                    dtype=torch.int64))
+        items = torch.cat(lists) if lists else torch.zeros(0, dtype=torch.int64)
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
+        raise ValueError(f"candidate row outside [0, {n_rows})")
+    if items.numel() and (int(items.min()) < 0 or int(items.max()) >= n_items):
+        raise ValueError(f"item id outside [0, {n_items})")
+    keys = torch.unique(rows * n_items + items)  # (sorted)
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64)
+    torch.cumsum(torch.bincount(keys // n_items, minlength=n_rows), 0, out=rowptr[1:])
+    return RowSets(rowptr.to(device), (keys % n_items).to(torch.int32).to(device), n_rows,
+                   n_items)
+
+
+def cand_segments(n_rows: int, max_len: int, k: int, device, cus: int | None = None) -> int:
+    """Segments per row (n_seg) for lg_score_topk_cand_f32, one wave each: 1 when the rows
+    alone fill the device (16 waves per compute unit), else as many as reach that target, no
+    segment shorter than CAND_MIN_SEG candidates, at most CAND_SEG_MAX. k is accepted for the
+    planner's signature; the plan does not depend on it. cus: the compute units to plan for
+    (default: `device`'s)."""
+    if cus is None:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+    n_rows, max_len, target = max(int(n_rows), 1), max(int(max_len), 1), 16 * int(cus)
+    if n_rows >= target:
+        return 1
+    return max(1, min(-(-target // n_rows), -(-max_len // CAND_MIN_SEG), CAND_SEG_MAX))
+
+
+def _cand_args(eu, ei, cand, excl, users, max_len):
+    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    nu, d = eu.shape
+    if ei.shape[1] != d:
+        raise ValueError("eu/ei dims differ")
+    if not isinstance(cand, RowSets):
+        raise ValueError("cand must be a RowSets (ops.candidate_rows)")
+    if cand.n_cols != ei.shape[0]:
+        raise ValueError(f"candidate columns {cand.n_cols} != items {ei.shape[0]}")
+    if excl is not None and excl.n_rows != nu:
+        raise ValueError(f"exclusion rows {excl.n_rows} != users {nu}")
+    if excl is not None and excl.col.numel() == 0:
+        excl = None  # (an empty tensor has no pointer to pass)
+    ids = None
+    if users is not None:
+        ids = _user_ids(users, nu, eu.device)
+        if int(ids.numel()) != cand.n_rows:
+            raise ValueError(f"{int(ids.numel())} users for {cand.n_rows} candidate rows")
+    elif cand.n_rows > nu:
+        raise ValueError(f"candidate rows {cand.n_rows} > users {nu}")
+    if max_len is None and cand.n_rows and cand.col.numel():
+        max_len = int(cand.degrees().max())  # (the one host read)
+    return eu, ei, excl, ids, max(int(max_len or 1), 1)
+
+
+def score_topk_cand(eu: torch.Tensor, ei: torch.Tensor, cand: RowSets, k: int,
+                    excl: RowSets | None = None, mask_value: float = MASK_VALUE, users=None,
+                    max_len: int | None = None, n_seg: int | None = None):
+    """Top-k of every row's OWN candidate list (lg_score_topk_cand_f32): (values fp32 [R, k],
+    ids int64 [R, k]), row r the first k of cand's row r scored for user users[r] (users=None:
+    user r) under (score desc, item id asc), real item ids, rows with fewer than k ranking
+    candidates padded with {-inf, -1}. The scores, the mask and the order are score_topk's:
+    row r equals score_topk(eu[u:u+1], ei[cand_r], k, ...) with the exclusion columns
+    renumbered and the ids mapped back, bit for bit; no row is gathered. cand: a RowSets over
+    the items (ops.candidate_rows); excl: the full tables' exclusion sets, indexed by user id.
+
+    max_len bounds the row length: candidates at positions >= max_len of their row are ignored.
+    max_len=None reads cand.degrees().max() -- one device-to-host read; pass max_len to stay
+    asynchronous. n_seg: segments per row (default: cand_segments); the result does not depend
+    on it. k > CAND_K_MAX raises. No rows or no candidates at all: padding, no launch."""
+    k = int(k)
+    if not 1 <= k <= CAND_K_MAX:
+        raise ValueError(f"k={k} not in [1, {CAND_K_MAX}]: lg_score_topk_cand_f32's limit is "
+                         f"{CAND_K_MAX}")
+    eu, ei, excl, ids, max_len = _cand_args(eu, ei, cand, excl, users, max_len)
+    dev, R, d = eu.device, cand.n_rows, eu.shape[1]
+    if R == 0 or cand.col.numel() == 0:
+        return _padding(R, k, dev)
+    ns = cand_segments(R, max_len, k, dev) if n_seg is None else int(n_seg)
+    ws_bytes = N.lib().lg_score_topk_cand_ws_bytes(R, d, k, ns)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    val = torch.empty((R, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((R, k), dtype=torch.int64, device=dev)
+    N.check(N.lib().lg_score_topk_cand_f32(
+        N.ptr(eu), N.ptr(ei), N.ptr(ids), R, eu.shape[0], ei.shape[0], N.ptr(cand.rowptr),
+        N.ptr(cand.col), max_len, d, N.ptr(excl.rowptr if excl else None),
+        N.ptr(excl.col if excl else None), float(mask_value), k, ns, N.ptr(val), N.ptr(idx),
+        N.ptr(ws), ws_bytes, N.stream_handle(dev)), "lg_score_topk_cand_f32")
+    return val, idx
+
+
+def score_cand(eu: torch.Tensor, ei: torch.Tensor, cand: RowSets,
+               excl: RowSets | None = None, mask_value: float = MASK_VALUE, users=None,
+               max_len: int | None = None) -> torch.Tensor:
+    """The scores of the (user, item) pairs of cand (lg_score_cand_f32): fp32 [nnz] in
+    cand.col's order, entry p the chain score of (users[r], cand.col[p]), r the row of p, or
+    mask_value where the item is in the user's exclusion row; -inf at positions >= max_len of
+    their row. Bit for bit score_topk_cand's values. max_len as in score_topk_cand (None: one
+    host read)."""
+    eu, ei, excl, ids, max_len = _cand_args(eu, ei, cand, excl, users, max_len)
+    dev = eu.device
+    # (-inf: entries of cand.col outside every row, as a row slice has, are not written)
+    out = torch.full((int(cand.col.numel()),), float("-inf"), dtype=torch.float32, device=dev)
+    if cand.n_rows == 0 or out.numel() == 0:
+        return out
+    N.check(N.lib().lg_score_cand_f32(
+        N.ptr(eu), N.ptr(ei), N.ptr(ids), cand.n_rows, eu.shape[0], ei.shape[0],
+        N.ptr(cand.rowptr), N.ptr(cand.col), max_len, eu.shape[1],
+        N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+        float(mask_value), N.ptr(out), N.stream_handle(dev)), "lg_score_cand_f32")
+    return out
+
+
 def score_dense(eu: torch.Tensor, ei: torch.Tensor, excl: RowSets | None = None,
                 mask_value: float = MASK_VALUE) -> torch.Tensor:
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")

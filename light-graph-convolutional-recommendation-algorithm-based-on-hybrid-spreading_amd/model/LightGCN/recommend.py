@@ -14,8 +14,9 @@ recommendForUsers is the request form: the same lists for a few user ids only, t
 ops.score_topk_users (lg_score_topk_batch_f32 for short lists: no rows gathered, no other
 user's scores computed). With items= it ranks a candidate item set only (the in-stock items,
 one category, a retrieval stage's output): lg_score_topk_batch_items_f32 for short lists, which
-gathers nothing and reads only the candidates' rows. recommendForAllUser keeps the
-reference's signature.
+gathers nothing and reads only the candidates' rows. recommendFromCandidates ranks every user
+over its OWN candidate list (a per-user retrieval stage's output, sampled negatives) in one
+launch of lg_score_topk_cand_f32. recommendForAllUser keeps the reference's signature.
 """
 import numpy as np
 import pandas as pd
@@ -96,6 +97,41 @@ def recommendForUsers(model, user_ids, user_num: int, item_num: int,
     ids = [int(u) for u in torch.as_tensor(user_ids).reshape(-1).tolist()]
     _, idx = topk_for_users(model, ids, user_num, item_num, train_edge_index, val_edge_index, k,
                             items=items)
+    rows = topk_to_dict(idx)
+    return {u: rows[j] for j, u in enumerate(ids)}
+
+
+def topk_for_candidates(model, candidates, user_num: int, item_num: int, train_edge_index,
+                        val_edge_index, k: int, user_ids=None):
+    """Device result of recommendFromCandidates: (scores [R,k] fp32, items [R,k] int64), row r
+    the top-k of row r's OWN candidate list for user user_ids[r] (None: user r), with
+    topk_for_users' mask and exclusions (ops.score_topk_cand: lg_score_topk_cand_f32, one
+    launch for every row, no row gathered). candidates: ops.candidate_rows' forms (a RowSets,
+    {row: ids}, a list of id lists, or a (rows, items) pair)."""
+    w_u = model.users_emb.weight.detach()
+    dev = gpu_device(w_u)
+    eu = w_u.to(dev, torch.float32).contiguous()
+    ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
+    n_rows = user_num if user_ids is None else int(torch.as_tensor(user_ids).numel())
+    cand = ops.candidate_rows(candidates, n_rows, item_num, dev)
+    excl = exclusion_from_coo(user_num, item_num, train_edge_index, val_edge_index, device=dev)
+    return ops.score_topk_cand(eu, ei, cand, k, excl, mask_value=float(-(1 << 10)),
+                               users=user_ids)
+
+
+def recommendFromCandidates(model, candidates, user_num: int, item_num: int,
+                            train_edge_index: torch.Tensor, val_edge_index: torch.Tensor,
+                            test_edge_index: torch.Tensor, k: int, user_ids=None) -> dict:
+    """{uid: top-k items} where every user is ranked over its own candidate list (a per-user
+    retrieval stage's output; the sampled-negative evaluation protocol): per user the list of
+    recommendForUsers(..., items=that user's candidates), in one launch. candidates row r
+    belongs to user user_ids[r] (None: user r, every user; ids should not repeat: the dict
+    keeps one list per id). Writes no file. A user or item id outside its table raises
+    ValueError. A user with fewer than k candidates that can rank gets a shorter list."""
+    ids = (list(range(user_num)) if user_ids is None
+           else [int(u) for u in torch.as_tensor(user_ids).reshape(-1).tolist()])
+    _, idx = topk_for_candidates(model, candidates, user_num, item_num, train_edge_index,
+                                 val_edge_index, k, user_ids=None if user_ids is None else ids)
     rows = topk_to_dict(idx)
     return {u: rows[j] for j, u in enumerate(ids)}
 

@@ -8,6 +8,7 @@ from lgcnhs.features import features_tensor
 from lgcnhs.recs import gpu_device, save_recs, topk_to_dict
 from model.LightGCN.recommend import buildGraph, topk_for_all_users  # noqa: F401
 from model.LightGCN.recommend import recommendForUsers, topk_for_users  # noqa: F401
+from model.LightGCN.recommend import recommendFromCandidates, topk_for_candidates  # noqa: F401
 from utils.log import logger
 
 
