@@ -352,6 +352,41 @@ int lg_score_cand_f32(const float *eu, const float *ei, const int64_t *user_ids,
                       const int64_t *ex_rowptr, const int32_t *ex_col, float mask_value,
                       float *out, lg_stream_t stream);
 
+/* The rank of given (user, item) pairs over the FULL catalog (csrc/rank.hip K2k): what an
+ * evaluation on held-out items asks (MRR, AUC, mean rank, recall / NDCG at any cut-off) and no
+ * list of k answers past position k. With v(u, j) = mask_value where j is in u's row of
+ * ex_rowptr / ex_col (the FULL table's exclusion CSR, indexed by user id), else the fp32 chain
+ * score of lg_score_topk_f32, and better(a, ja, b, jb) = a > b || (a == b && ja < jb):
+ *     rank(u, i) = #{ j in [0, n_items), j != i : better(v(u, j), j, v(u, i), i) }   (0 = first)
+ * Excluded items rank at mask_value, an excluded target has v = mask_value, NaN follows the
+ * formula literally (never better; nothing is better than a NaN target). For finite scores and
+ * k <= 1024: rank < k iff the top-k list of u holds i at position rank. Rows follow
+ * lg_score_topk_cand_f32's conventions: row r belongs to user user_ids[r] (device, int64; NULL:
+ * user r), its targets are tgt_col[tgt_rowptr[r] .. tgt_rowptr[r + 1]) (device, int64 / int32),
+ * in any order. out_rank (device, int64) and out_score (device, fp32) have one entry per entry of
+ * tgt_col; out_score gets v(u, i). max_targets in [1, LG_RANK_ROW_MAX] is the caller's bound on a
+ * row's length: positions >= max_targets of a row get {-1, -inf} (defined, not an error; a longer
+ * list is several rows with the same user id). A target id outside [0, n_items) gets {-1, -inf},
+ * a user id outside [0, n_table_users) {-1, -inf} for its whole row; memory-safe on any input.
+ * The items are counted in n_splits in [1, 4096] ranges of split_len(n_items, n_splits) items;
+ * integer counts: the result does not depend on n_splits. The workspace holds a threshold and an
+ * id per target slot and one int32 count per (split, slot): lg_score_rank_ws_bytes(n_rows,
+ * n_targets, dim, n_splits) = n_targets x (8 + 4 n_splits) with n_targets = n_rows x max_targets,
+ * the slots of the call (0 for arguments the call refuses). dim in {32, 64, 128}, n_items <
+ * 2^31 - 1. */
+#define LG_RANK_ROW_MAX 4
+size_t lg_score_rank_ws_bytes(int64_t n_rows, int64_t n_targets, int32_t dim, int32_t n_splits);
+/* LG_ERR_ARG on a null pointer (user_ids and the exclusion pair may be NULL), n_rows < 1 or
+ * n_rows x n_splits past the grid limit, bad n_table_users, n_items, max_targets, dim or
+ * n_splits, a half-set exclusion pair; LG_ERR_WORKSPACE when ws is NULL or short; all before any
+ * launch. Never allocates, never syncs. */
+int lg_score_rank_f32(const float *eu, const float *ei, const int64_t *user_ids, int64_t n_rows,
+                      int64_t n_table_users, int64_t n_items, const int64_t *tgt_rowptr,
+                      const int32_t *tgt_col, int32_t max_targets, int32_t dim,
+                      const int64_t *ex_rowptr, const int32_t *ex_col, float mask_value,
+                      int32_t n_splits, int64_t *out_rank, float *out_score, void *ws,
+                      size_t ws_bytes, lg_stream_t stream);
+
 /* Dense masked score matrix G[u][i] (same score definition and mask as above), written
  * with leading dimension ldg. Replaces getAllocateMat's matmul + masks
  * (model/SpreadLightGCN/model.py:74-104, model/SpreadLightGCNOpti/model.py:139-169). */

@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("LGCNHS_LIB_PATH") or LIB_PATH
 LG_OK = 0
 LG_ACC_NONE, LG_ACC_FIRST, LG_ACC_MID, LG_ACC_LAST, LG_ACC_ONLY = 0, 1, 2, 3, 4
 LG_EXCL_DROP, LG_EXCL_NONE = 0, 1
+LG_RANK_ROW_MAX = 4  # include/lgcnhs.h
 ABI_VERSION = 17
 
 _vp = ctypes.c_void_p
@@ -106,6 +107,12 @@ SIGNATURES = {
     "lg_score_cand_f32": (
         ctypes.c_int,
         [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp],
+    ),
+    "lg_score_rank_ws_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "lg_score_rank_f32": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp,
+         _vp, _sz, _vp],
     ),
     "lg_score_topk_screened_f32": (
         ctypes.c_int,

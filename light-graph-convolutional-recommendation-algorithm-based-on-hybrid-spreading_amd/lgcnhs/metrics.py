@@ -7,10 +7,13 @@ pair_overlap        sum_{u != v} |R_u & R_v|, exact (diversity.py:15-63)  lg_rec
 hamming             calHammingDistance's value, unrounded
 intra_similarity    calInternalSimilarity's value, unrounded             lg_rec_intra_similarity_f64
                     (diversity.py:66-115)
+rank_metrics        MRR, mean rank, AUC and P / R / NDCG at any cut-offs from full-catalog ranks
+                    (ops.score_rank, lg_score_rank_f32); plain torch on the ranks' device
 
 The reference-signature wrappers (dicts, numpy matrices, 5-decimal rounding, float32 torch
 reductions) are metrics/accurate.py and metrics/diversity.py of this package.
-No CPU fallback: GPU tensors only.
+No CPU fallback: GPU tensors only (rank_metrics, a few reductions over [nnz] integers, runs where
+its ranks are).
 """
 from __future__ import annotations
 
@@ -109,3 +112,69 @@ def intra_similarity(recs: torch.Tensor, by_item: RowSets, item_degree: torch.Te
     total = 2.0 * float(intra_similarity_parts(recs, by_item, item_degree).sum())
     return total / (recs.shape[0] * k * (k - 1))
 
+
+
+def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,)) -> dict:
+    """Ranking metrics from the full-catalog ranks of held-out items (ops.score_rank): `rank`
+    int64 [nnz] aligned with targets.col (0 = first, -1 = not ranked), one row of `targets` per
+    user. Plain torch on rank's device, fp64. Targets with rank -1 are left out and counted in
+    n_skipped; users left with no target are not averaged. With n_t a user's evaluated targets:
+
+    mrr           mean over users of 1 / (1 + the user's best rank)
+    mean_rank     mean over all evaluated targets of rank
+    auc           mean over users of 1 - mean_i((rank_i - a_i) / (n_items - n_t)), a_i the number of
+                  the user's own targets ranked above i: the share of (target, other item) pairs
+                  the model orders correctly
+    precision@k, recall@k, ndcg@k for every k in ks, from rank < k with metrics.accuracy's
+                  definitions (hits / k, hits / n_t, DCG over the ideal DCG of k ones)
+    n_eval        the users averaged over."""
+    n_items = int(n_items)
+    rank = rank.reshape(-1).to(torch.int64)
+    dev = rank.device
+    rp = targets.rowptr.to(dev)
+    R = targets.n_rows
+    if int(rank.numel()) != int(targets.col.numel()):
+        raise ValueError(f"{int(rank.numel())} ranks for {int(targets.col.numel())} targets")
+    pos = torch.arange(rank.numel(), dtype=torch.int64, device=dev)
+    row = torch.searchsorted(rp, pos, right=True) - 1
+    inside = (row >= 0) & (row < R)
+    ok = inside & (rank >= 0)
+    out = {"n_skipped": int((inside & (rank < 0)).sum())}
+    row, rk = row[ok], rank[ok]
+    n_t = torch.bincount(row, minlength=R).to(torch.float64)
+    ev = n_t > 0
+    n_eval = int(ev.sum())
+    out["n_eval"] = n_eval
+    names = ["mrr", "mean_rank", "auc"] + [f"{m}@{int(k)}" for k in ks
+                                           for m in ("precision", "recall", "ndcg")]
+    if n_eval == 0:
+        out.update({n: float("nan") for n in names})
+        return out
+    f64 = rk.to(torch.float64)
+    zeros = torch.zeros(R, dtype=torch.float64, device=dev)
+
+    def user_mean(per_user):
+        return float(per_user[ev].mean())
+
+    best = torch.full((R,), n_items, dtype=torch.int64, device=dev)
+    best.scatter_reduce_(0, row, rk, "amin")
+    out["mrr"] = user_mean(1.0 / (1.0 + best.to(torch.float64)))
+    out["mean_rank"] = float(f64.mean())
+    # a_i: the position of i among its user's targets by rank
+    order = torch.argsort(row * (n_items + 1) + rk)
+    first = torch.cumsum(n_t, 0) - n_t  # the first sorted position of every user
+    a = torch.empty_like(f64)
+    a[order] = torch.arange(rk.numel(), dtype=torch.float64, device=dev) - first[row[order]]
+    others = (n_items - n_t).clamp(min=1.0)
+    out["auc"] = user_mean(1.0 - zeros.index_add(0, row, (f64 - a) / others[row])
+                           / n_t.clamp(min=1.0))
+    gain = 1.0 / torch.log2(f64 + 2.0)
+    for k in ks:
+        k = int(k)
+        hit = (rk < k).to(torch.float64)
+        n = zeros.index_add(0, row, hit)
+        idcg = float((1.0 / torch.log2(torch.arange(2, k + 2, dtype=torch.float64))).sum())
+        out[f"precision@{k}"] = user_mean(n) / k
+        out[f"recall@{k}"] = user_mean(n / n_t.clamp(min=1.0))
+        out[f"ndcg@{k}"] = user_mean(zeros.index_add(0, row, hit * gain) / (idcg if idcg else 1.0))
+    return out

@@ -936,6 +936,119 @@ def score_cand(eu: torch.Tensor, ei: torch.Tensor, cand: RowSets,
     return out
 
 
+RANK_ROW_MAX = N.LG_RANK_ROW_MAX  # targets per kernel row of lg_score_rank_f32 (csrc/rank.hip)
+RANK_SPLITS_MAX = 4096           # ... and its most item ranges
+RANK_ROWS_PER_WAVE = 32          # k_rank_count: 2 groups of 16 rows per wave, 4 waves per block
+# rank_splits' constants, from the `split_sweep` of profiles/score_rank.json
+# (scripts/score_rank_time.py, 1M items, d = 64). Many rows: the time falls with the waves on the
+# device well past the resident set -- 32,768 users x 1 target 40.8 / 33.9 / 32.0 / 31.7 / 31.5 ms
+# at 1 / 2 / 4 / 8 / 16 splits (4 .. 64 waves per compute unit), x 4 targets 67.2 / 48.3 / 43.8 /
+# 42.2 / 41.3, 13,312 kernel rows 63.1 / 24.6 / 17.5 / 16.3 at 1 / 4 / 8 / 16 -- and gains under
+# 2 % past 32 waves per compute unit at 32,768 users. Few rows: 16 and 64 users are fastest from 976
+# splits of 1,024 items on (0.15 ms against 0.23 ms at 244 splits of 4,096); shorter splits gain
+# nothing and lengthen k_rank_finish's sum.
+RANK_WAVES_PER_CU = 32
+RANK_MIN_SPLIT = 1024
+
+
+def rank_splits(n_rows: int, n_items: int, device, cus: int | None = None) -> int:
+    """Item ranges (n_splits) for lg_score_rank_f32: 1 when the rows alone give the device
+    RANK_WAVES_PER_CU waves per compute unit (a wave counts for 32 rows), else as many as reach
+    that target, no range shorter than RANK_MIN_SPLIT items (nor than 16), at most
+    RANK_SPLITS_MAX. The ranks do not depend on it. cus: the compute units to plan for
+    (default: `device`'s)."""
+    if cus is None:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+    waves = max(-(-max(int(n_rows), 1) // RANK_ROWS_PER_WAVE), 1)
+    target = RANK_WAVES_PER_CU * int(cus)
+    if waves >= target:
+        return 1
+    return max(1, min(-(-target // waves), int(n_items) // RANK_MIN_SPLIT, RANK_SPLITS_MAX))
+
+
+def rank_plan_rows(n_rows: int, nnz: int, row_max: int = RANK_ROW_MAX) -> int:
+    """The kernel rows rank_splits should plan for, from what the host knows (target rows and
+    entries): at least ceil(nnz / row_max), about one per row when rows are short, never more
+    than rank_rows' bound. Exact when every row has the same number of targets <= row_max; the
+    real count is read nowhere."""
+    n_rows, nnz, M = int(n_rows), int(nnz), int(row_max)
+    bound = (nnz + (M - 1) * min(n_rows, nnz)) // M
+    return max(1, min(bound, max(-(-nnz // M), min(n_rows, nnz))))
+
+
+def rank_rows(targets: RowSets, users: torch.Tensor | None = None,
+              row_max: int = RANK_ROW_MAX):
+    """The kernel rows of lg_score_rank_f32 for target rows of any length: (rowptr int64
+    [K + 1], user ids int64 [K]). Row r of `targets` with n > 0 targets becomes ceil(n / row_max)
+    kernel rows over consecutive runs of its own entries of targets.col, so the kernel's outputs
+    stay aligned with targets.col; a row without targets gets none. users: the user id of every
+    target row (None: row r is user r). Tensor arithmetic on targets' device, no host read: K is
+    the bound (nnz + (row_max - 1) min(n_rows, nnz)) // row_max on the sum of the ceilings, the
+    kernel rows past the real ones are empty (user 0) and cost the kernel nothing."""
+    rp = targets.rowptr
+    dev = rp.device
+    R, nnz, M = targets.n_rows, int(targets.col.numel()), int(row_max)
+    if R == 0:
+        return rp[:1].clone(), torch.zeros(0, dtype=torch.int64, device=dev)
+    K = (nnz + (M - 1) * min(R, nnz)) // M
+    deg = rp[1:] - rp[:-1]
+    kend = torch.cumsum((deg + (M - 1)) // M, 0)  # kernel rows of target rows [0, r]
+    j = torch.arange(K + 1, dtype=torch.int64, device=dev)
+    src = torch.searchsorted(kend, j, right=True)  # the target row of kernel row j; R: padding
+    real = src < R
+    srcc = src.clamp(max=max(R - 1, 0))
+    kstart = kend - (deg + (M - 1)) // M
+    # padding rows and the closing pointer sit at the end of the last row: empty rows
+    krp = torch.where(real, rp[srcc] + (j - kstart[srcc]) * M, rp[R:R + 1].expand(K + 1))
+    ids = srcc if users is None else users.to(dev, torch.int64)[srcc]
+    ids = torch.where(real, ids, torch.zeros_like(ids))[:K]
+    return krp.contiguous(), ids.contiguous()
+
+
+def score_rank(eu: torch.Tensor, ei: torch.Tensor, targets, excl: RowSets | None = None,
+               users=None, mask_value: float = MASK_VALUE, n_splits: int | None = None):
+    """Where the given (user, item) pairs stand among ALL items (lg_score_rank_f32): (rank int64
+    [nnz], score fp32 [nnz]) aligned with the target CSR's col -- rank the number of items that
+    come before the target in score_topk's order (score desc, item id asc; excluded items and an
+    excluded target at mask_value), 0 = first, and score the target's own value. For finite
+    scores rank < k iff score_topk's list of that user holds the item at position rank. The
+    held-out-item question of an evaluation (lgcnhs.metrics.rank_metrics takes the ranks).
+
+    targets: anything ops.candidate_rows takes (a dict, one list per row, a (rows, items) pair, a
+    RowSets), one row per user -- or per entry of `users`, which has score_topk_cand's meaning.
+    Rows of any length: rows longer than RANK_ROW_MAX become several kernel rows (rank_rows; no
+    host read). excl: the full tables' exclusion sets, indexed by user id. n_splits: item ranges
+    (default: rank_splits); the result does not depend on it. An entry of a RowSets' col outside
+    every row, and a target id outside the items, gets {-1, -inf}. No targets: empty tensors (or
+    all {-1, -inf}), no launch."""
+    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    nu, d = eu.shape
+    dev = eu.device
+    R = nu if users is None else int(torch.as_tensor(users).numel())
+    if isinstance(targets, RowSets):
+        R = targets.n_rows  # (checked against users by _cand_args)
+    targets = candidate_rows(targets, R, ei.shape[0], dev)
+    eu, ei, excl, ids, _ = _cand_args(eu, ei, targets, excl, users, 1)  # (max_len: no read)
+    nnz = int(targets.col.numel())
+    rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+    score = torch.full((nnz,), float("-inf"), dtype=torch.float32, device=dev)
+    if R == 0 or nnz == 0:
+        return rank, score
+    krp, kids = rank_rows(targets, ids)
+    K = int(kids.numel())
+    # (planned on the likely count of non-empty kernel rows: the padding rows stream nothing)
+    ns = rank_splits(rank_plan_rows(R, nnz), ei.shape[0], dev) if n_splits is None \
+        else int(n_splits)
+    ws_bytes = N.lib().lg_score_rank_ws_bytes(K, K * RANK_ROW_MAX, d, ns)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    N.check(N.lib().lg_score_rank_f32(
+        N.ptr(eu), N.ptr(ei), N.ptr(kids), K, nu, ei.shape[0], N.ptr(krp), N.ptr(targets.col),
+        RANK_ROW_MAX, d, N.ptr(excl.rowptr if excl else None),
+        N.ptr(excl.col if excl else None), float(mask_value), ns, N.ptr(rank), N.ptr(score),
+        N.ptr(ws), ws_bytes, N.stream_handle(dev)), "lg_score_rank_f32")
+    return rank, score
+
+
 def score_dense(eu: torch.Tensor, ei: torch.Tensor, excl: RowSets | None = None,
                 mask_value: float = MASK_VALUE) -> torch.Tensor:
     eu, ei = _f32(eu, "eu"), _f32(ei, "ei")

@@ -9,7 +9,10 @@ lg_score_topk_f32 below it -- the ML-100K / ML-1M evaluations --, lists bit for 
 same; 128 < k <= 1024: lg_score_topk_wide_f32, the same lists from global slabs; ties ordered
 by (score desc, item asc));
 the val adjacency is accepted and unused, as in
-the reference (it converts it at :38 and never reads it). calValLoss runs the forward on the
+the reference (it converts it at :38 and never reads it). getHeldOutRanks is the call the
+reference lacks: the full-catalog rank of every held-out edge under the same scores and mask
+(ops.score_rank, lg_score_rank_f32; lgcnhs.metrics.rank_metrics turns the ranks into MRR, AUC
+and recall / NDCG at any cut-off). calValLoss runs the forward on the
 val adjacency (HIP propagation), draws one negative per val edge (structured negative
 sampling, on the device) and returns the BPR loss of those triples rounded to 5 decimals
 (reference :56-86)."""
@@ -34,6 +37,22 @@ def getValRecommendations(model, user_num: int, item_num: int, train_edge_index,
     excl = exclusion_from_coo(user_num, item_num, train_edge_index, device=dev)
     _, idx = ops.score_topk(eu, ei, k, excl, mask_value=MASK_VALUE)
     return idx
+
+
+def getHeldOutRanks(model, user_num: int, item_num: int, train_edge_index, held_edge_index):
+    """(targets RowSets, rank int64 [nnz]): where every held-out edge's item stands among all
+    items for its user, under getValRecommendations' scores -- layer-0 embeddings, the TRAIN
+    positives at -1024, (score desc, item asc). `targets` holds the held-out positives, one row
+    per user; rank is aligned with targets.col (0 = first); rank < k iff getValRecommendations
+    (k) lists the item at that position."""
+    w_u = model.users_emb.weight.detach()
+    dev = gpu_device(w_u)
+    eu = w_u.to(dev, torch.float32).contiguous()
+    ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
+    excl = exclusion_from_coo(user_num, item_num, train_edge_index, device=dev)
+    targets = exclusion_from_coo(user_num, item_num, held_edge_index, device=dev)
+    rank, _ = ops.score_rank(eu, ei, targets, excl, mask_value=MASK_VALUE)
+    return targets, rank
 
 
 def val_loss_for_triples(model, val_edge_index, users, pos, neg, lambda_val: float) -> float:
