@@ -188,6 +188,23 @@ class RowSets:
     """Sorted, de-duplicated column sets per row: (rowptr int64 [n_rows+1], col int32)."""
 
     def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, n_rows: int, n_cols: int):
+        # the kernels read rowptr as int64 and col as int32 words: any other type would be
+        # reinterpreted, not converted. (Sortedness stays the caller's contract: checking it
+        # would read device memory on the host.)
+        for t, name, dtype in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+            if t.dtype != dtype:
+                raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got "
+                                f"{t.dtype}")
+            if t.dim() != 1:
+                raise ValueError(f"{name} must be 1-D, got shape {tuple(t.shape)}")
+        if rowptr.numel() != int(n_rows) + 1:
+            raise ValueError(f"rowptr has {rowptr.numel()} entries for {int(n_rows)} rows "
+                             f"(expected {int(n_rows) + 1})")
+        if rowptr.device != col.device:
+            raise ValueError(f"rowptr is on {rowptr.device}, col on {col.device}")
+        rowptr, col = rowptr.contiguous(), col.contiguous()
         if col.numel() == 0 and col.data_ptr() == 0:
             # an empty set still passes a valid device pointer: the C ABI refuses NULL columns
             col = torch.empty(1, dtype=col.dtype, device=col.device)[:0]

@@ -28,11 +28,66 @@ from .graph import Adjacency, RowSets
 MASK_VALUE = float(-(1 << 10))  # model/LightGCN/recommend.py:101,111
 
 
-def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """t contiguous with a 16-byte aligned base address, as the kernels' vector loads assume
+    (a copy when it is not: a column slice, a transposed table, a stride-0 gradient, a view at
+    an odd element offset of another tensor)."""
+    t = t.contiguous()
+    if t.numel() and t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _typed(t, name: str, dtype, rank: int = 2) -> None:
+    """TypeError unless t is a tensor of `dtype`, ValueError unless it has `rank` dimensions
+    (no device check: a CPU tensor gets the same messages)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
+    if t.dim() != rank:
+        raise ValueError(f"{name} must have {rank} dimensions, got shape {tuple(t.shape)}")
+
+
+def _dense(t, name: str, dtype, rank: int = 2) -> torch.Tensor:
+    """A dense kernel operand: _typed, on the GPU, then _aligned."""
+    _typed(t, name, dtype, rank)
     N.require_gpu(t, name)
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
-    return t.contiguous()
+    return _aligned(t)
+
+
+def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _dense(t, name, torch.float32)
+
+
+def _f32_tables(eu: torch.Tensor, ei: torch.Tensor):
+    """_f32 of the user and item tables, both types checked before either device."""
+    _typed(eu, "eu", torch.float32)
+    _typed(ei, "ei", torch.float32)
+    return _f32(eu, "eu"), _f32(ei, "ei")
+
+
+def _f64(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _dense(t, name, torch.float64)
+
+
+def _same_device(t: torch.Tensor, name: str, ref: torch.Tensor, ref_name: str) -> None:
+    if t.device != ref.device:
+        raise ValueError(f"{name} is on {t.device}, {ref_name} on {ref.device}")
+
+
+def _layer_operand(t, name: str, x: torch.Tensor, dtype) -> None:
+    """y / x0 / acc / out of run_layer: None, or x's shape and device, contiguous, of `dtype`."""
+    if t is None:
+        return
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
+    if t.shape != x.shape or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous of x's shape {tuple(x.shape)}, got "
+                         f"shape {tuple(t.shape)} strides {t.stride()}")
+    _same_device(t, name, x, "x")
+    if t.numel() and t.data_ptr() % 16:
+        raise ValueError(f"{name} must start at a 16-byte aligned address")
 
 
 # ------------------------------------------------------------------------------ propagation
@@ -44,30 +99,49 @@ def run_layer(rowptr, src, dis, w, x, y, x0, acc, out, n_rows: int, row_offset: 
     and, when the slice has rows above the long-row threshold, lg_spmm_long_rows_f32 (its
     masked form with row_mask). A float16 ``x`` (fp16 layer storage, inference) goes to
     lg_spmm_layer_f16 / lg_spmm_long_rows_f16: ``y`` is then float16 or None, and live /
-    row_mask (training paths) are refused."""
+    row_mask (training paths) are refused. x is contiguous [nodes, dim] at a 16-byte aligned
+    address and covers rows [row_offset, row_offset + n_rows); y has x's dtype, x0 / acc / out
+    are float32, each None or of x's shape on x's device."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"x must be a float32 or float16 tensor, got "
+                        f"{getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"x must be contiguous [nodes, dim], got shape {tuple(x.shape)} "
+                         f"strides {x.stride()}")
+    if row_offset < 0 or n_rows < 0 or row_offset + n_rows > x.shape[0]:
+        raise ValueError(f"rows [{row_offset}, {row_offset + n_rows}) outside x's "
+                         f"{x.shape[0]} rows")
+    if x.numel() and x.data_ptr() % 16:
+        raise ValueError("x must start at a 16-byte aligned address")
+    if x.dtype == torch.float16 and y is not None and y.dtype != torch.float16:
+        raise ValueError(f"a float16 x needs a float16 y (or None), got {y.dtype}")
+    _layer_operand(y, "y", x, x.dtype)
+    for t, name in ((x0, "x0"), (acc, "acc"), (out, "out")):
+        _layer_operand(t, name, x, torch.float32)
+    half = x.dtype == torch.float16
+    if half and (live is not None or row_mask is not None):
+        raise ValueError("float16 layer storage is inference-only: no live / row_mask")
+    if row_mask is not None and live is not None:
+        raise ValueError("row_mask and live are exclusive")
+    for m, name in ((live, "live"), (row_mask, "row_mask")):
+        if m is not None and (m.dtype != torch.uint8 or m.numel() != x.shape[0]
+                              or m.device != x.device or not m.is_contiguous()):
+            raise ValueError(f"{name} must be a uint8 mask with one entry per row of x")
+    N.require_gpu(x, "x")
     dim = x.shape[1]
     thr = plan.threshold if (plan is not None and plan.n_long) else 0
     strm = N.stream_handle(x.device)
-    half = x.dtype == torch.float16
     if half:
-        if live is not None or row_mask is not None:
-            raise ValueError("float16 layer storage is inference-only: no live / row_mask")
-        if y is not None and y.dtype != torch.float16:
-            raise ValueError(f"a float16 x needs a float16 y (or None), got {y.dtype}")
         N.check(N.lib().lg_spmm_layer_f16(
             N.ptr(rowptr), N.ptr(src), N.ptr(dis), N.ptr(w), N.ptr(x), N.ptr(y), N.ptr(x0),
             N.ptr(acc), N.ptr(out), n_rows, row_offset, dim, mode, float(denom), thr, strm),
             "lg_spmm_layer_f16")
     elif row_mask is not None:
-        if live is not None:
-            raise ValueError("row_mask and live are exclusive")
         N.check(N.lib().lg_spmm_layer_rows_f32(
             N.ptr(rowptr), N.ptr(src), N.ptr(dis), N.ptr(w), N.ptr(x), N.ptr(y), N.ptr(x0),
             N.ptr(acc), N.ptr(out), n_rows, row_offset, dim, mode, float(denom), thr,
             N.ptr(row_mask), strm), "lg_spmm_layer_rows_f32")
     elif live is not None:
-        if live.dtype != torch.uint8 or live.numel() != x.shape[0] or live.device != x.device:
-            raise ValueError("live must be a uint8 mask with one entry per row of x")
         N.check(N.lib().lg_spmm_layer_live_f32(
             N.ptr(rowptr), N.ptr(src), N.ptr(dis), N.ptr(w), N.ptr(x), N.ptr(y), N.ptr(x0),
             N.ptr(acc), N.ptr(out), n_rows, row_offset, dim, mode, float(denom), thr,
@@ -98,6 +172,8 @@ def spmm_layer(adj: Adjacency, x: torch.Tensor, y, x0, acc, out, mode: int, deno
     """One layer over all rows of ``adj`` (or the rows ``row_mask`` marks); with
     stream_weights the precomputed gcn_norm edge weights are streamed (else recomputed from
     dis; identical values); with long_rows, hub rows go through the segmented path."""
+    if isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[0] != adj.n_nodes:
+        raise ValueError(f"x has {x.shape[0]} rows, graph has {adj.n_nodes} nodes")
     w = adj.edge_weight() if stream_weights else None
     run_layer(adj.rowptr, adj.src, adj.dis(), w, x, y, x0, acc, out, adj.n_nodes, 0, mode,
               denom, adj.long_plan() if long_rows else None, live, row_mask)
@@ -113,6 +189,13 @@ def live_rows(x: torch.Tensor) -> torch.Tensor:
 
 def rows_to_f16(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """f16(x) of an fp32 [n, d] array, round to nearest even (lg_rows_f32_to_f16)."""
+    _typed(x, "x", torch.float32)
+    if out is not None:
+        _typed(out, "out", torch.float16)
+        if out.shape != x.shape or not out.is_contiguous():
+            raise ValueError(f"out must be contiguous of x's shape {tuple(x.shape)}, got "
+                             f"shape {tuple(out.shape)} strides {out.stride()}")
+        _same_device(out, "out", x, "x")
     x = _f32(x, "x")
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
@@ -469,7 +552,7 @@ def score_topk(eu: torch.Tensor, ei: torch.Tensor, k: int, excl: RowSets | None 
     the ids back: real item ids, rows shorter than k padded with {-inf, -1}. The gather is
     noise next to the scoring of every user; the request form that gathers nothing is
     score_topk_users(items=...)."""
-    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    eu, ei = _f32_tables(eu, ei)
     nu, d = eu.shape
     ni = ei.shape[0]
     k = int(k)
@@ -630,7 +713,7 @@ def _user_ids(users, n_users: int, device) -> torch.Tensor:
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n_users):
             raise ValueError(f"user id outside [0, {n_users})")
         t = t.to(device)
-    return t.contiguous()
+    return _aligned(t)
 
 
 ITEMS_CALL_USERS = 16  # users per lg_score_topk_batch_items_f32 call (csrc/topk_items.hip)
@@ -665,7 +748,7 @@ def item_candidates(items, n_items: int, device) -> torch.Tensor:
         raise ValueError("item ids must be integers")
     t = t.reshape(-1)
     if t.is_cuda:
-        return t.to(device, torch.int32).contiguous()
+        return _aligned(t.to(device, torch.int32))
     t = torch.unique(t.to(torch.int64))  # (sorted)
     if t.numel() and (int(t[0]) < 0 or int(t[-1]) >= n_items):
         raise ValueError(f"item id outside [0, {n_items})")
@@ -735,7 +818,7 @@ def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
     ITEMS_BATCH_MAX_USERS users (k <= 128) run lg_score_topk_batch_items_f32 in chunks of 16
     -- no item row is gathered and only the candidates' rows are read; longer lists and k > 128
     run score_topk on the gathered sub-table. Empty candidates give all padding."""
-    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    eu, ei = _f32_tables(eu, ei)
     nu, d = eu.shape
     ni = ei.shape[0]
     k = int(k)
@@ -854,7 +937,7 @@ def cand_segments(n_rows: int, max_len: int, k: int, device, cus: int | None = N
 
 
 def _cand_args(eu, ei, cand, excl, users, max_len):
-    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    eu, ei = _f32_tables(eu, ei)
     nu, d = eu.shape
     if ei.shape[1] != d:
         raise ValueError("eu/ei dims differ")
@@ -1021,7 +1104,7 @@ def score_rank(eu: torch.Tensor, ei: torch.Tensor, targets, excl: RowSets | None
     (default: rank_splits); the result does not depend on it. An entry of a RowSets' col outside
     every row, and a target id outside the items, gets {-1, -inf}. No targets: empty tensors (or
     all {-1, -inf}), no launch."""
-    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    eu, ei = _f32_tables(eu, ei)
     nu, d = eu.shape
     dev = eu.device
     R = nu if users is None else int(torch.as_tensor(users).numel())
@@ -1051,7 +1134,7 @@ def score_rank(eu: torch.Tensor, ei: torch.Tensor, targets, excl: RowSets | None
 
 def score_dense(eu: torch.Tensor, ei: torch.Tensor, excl: RowSets | None = None,
                 mask_value: float = MASK_VALUE) -> torch.Tensor:
-    eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+    eu, ei = _f32_tables(eu, ei)
     nu, d = eu.shape
     ni = ei.shape[0]
     G = torch.empty((nu, ni), dtype=torch.float32, device=eu.device)
@@ -1097,8 +1180,8 @@ def spread_general(A: Interactions) -> torch.Tensor:
 def hybrid_weight(gW: torch.Tensor, k_item: torch.Tensor, lam: float,
                   transpose: bool = False) -> torch.Tensor:
     N.require_gpu(gW, "gW")
-    gW = gW.contiguous().to(torch.float64)
-    k_item = k_item.contiguous().to(torch.float64)
+    gW = _aligned(gW.to(torch.float64))
+    k_item = _aligned(k_item.to(torch.float64))
     W = torch.empty_like(gW)
     N.check(N.lib().lg_hybrid_weight_f64(N.ptr(gW), N.ptr(k_item), gW.shape[0], float(lam),
                                          int(bool(transpose)), N.ptr(W),
@@ -1123,10 +1206,25 @@ def spread_hybrid(A: Interactions, lam: float) -> torch.Tensor:
 
 def spread_resource(A: Interactions, W: torch.Tensor, users: slice | None = None,
                     out: torch.Tensor | None = None) -> torch.Tensor:
-    """F rows for users [u0, u1) (all by default)."""
+    """F rows for users [u0, u1) (all by default). W: float64 [I, I] on A's device. out: a
+    float64 buffer of at least [u1 - u0, I] with unit column stride (rows [0, u1 - u0) and
+    columns [0, I) are written; its row stride is kept)."""
     u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
-    W = W.contiguous()
-    F = out if out is not None else torch.empty((u1 - u0, A.n_items), dtype=torch.float64,
+    I = A.n_items
+    _typed(W, "W", torch.float64)
+    if tuple(W.shape) != (I, I):
+        raise ValueError(f"W has shape {tuple(W.shape)}, expected ({I}, {I})")
+    _same_device(W, "W", A.by_user.col, "A")
+    if not 0 <= u0 <= u1 <= A.n_users:
+        raise ValueError(f"users [{u0}, {u1}) outside [0, {A.n_users}]")
+    if out is not None:
+        _typed(out, "out", torch.float64)
+        if out.shape[0] < u1 - u0 or out.shape[1] < I or (out.numel() and out.stride(1) != 1):
+            raise ValueError(f"out has shape {tuple(out.shape)} strides {out.stride()}, "
+                             f"expected at least ({u1 - u0}, {I}) with unit column stride")
+        _same_device(out, "out", W, "W")
+    W = _f64(W, "W")
+    F = out if out is not None else torch.empty((u1 - u0, I), dtype=torch.float64,
                                                 device=W.device)
     N.check(N.lib().lg_spread_resource_f64(
         N.ptr(A.by_user.rowptr[u0:]), N.ptr(A.by_user.col), N.ptr(W), u1 - u0, A.n_items,
@@ -1143,15 +1241,22 @@ def rows_topk(F: torch.Tensor, k: int, excl: RowSets | None = None, drop: bool =
     k = int(k)
     if k < 1 or k > 1024:
         raise ValueError(f"k={k} not in [1, 1024]")
-    N.require_gpu(F, "F")
-    if F.dtype != torch.float64:
-        raise TypeError("F must be float64")
-    if F.stride(1) != 1:
-        F = F.contiguous()
+    _typed(F, "F", torch.float64)
     n, m = F.shape
+    if eu is not None:
+        _typed(eu, "eu", torch.float32)
+        _typed(ei, "ei", torch.float32)
+        if eu.shape[0] != n or ei.shape[0] != m or eu.shape[1] != ei.shape[1]:
+            raise ValueError(f"F is {n} x {m}: eu must be [{n}, d] and ei [{m}, d], got "
+                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+    if excl is not None and excl.n_rows != n:
+        raise ValueError(f"exclusion rows {excl.n_rows} != rows of F {n}")
+    N.require_gpu(F, "F")
+    if F.numel() and (F.stride(1) != 1 or F.data_ptr() % 16):
+        F = _aligned(F)  # (a row-strided view of a larger buffer is taken as it is)
     d = 0
     if eu is not None:
-        eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+        eu, ei = _f32_tables(eu, ei)
         d = eu.shape[1]
     val = torch.empty((n, k), dtype=torch.float64, device=F.device)
     idx = torch.empty((n, k), dtype=torch.int64, device=F.device)
@@ -1744,9 +1849,37 @@ def chunk_bounds(ub, un, ib, inorm, dim: int, j0: int, width: int,
     chunk of items [j0, j0 + width) (lg_score_chunk_bound); with qout ([users, qstride]
     uint8, qstride >= width rounded up to 256) also the per-column 8-bit bounds. Returns gb,
     or (gb, q) with qout. width <= 4096 (LG_BOUND_MAX_WIDTH; the library refuses wider
-    tiles)."""
+    tiles). ub / ib: bound_operands' int16 [rows, dim] bf16 copies, un / inorm their float32
+    norms; items [j0, j0 + width) lie inside ib."""
+    dim, j0, width = int(dim), int(j0), int(width)
+    _typed(ub, "ub", torch.int16)
+    _typed(ib, "ib", torch.int16)
+    _typed(un, "un", torch.float32, 1)
+    _typed(inorm, "inorm", torch.float32, 1)
+    if ub.shape[1] != dim or ib.shape[1] != dim:
+        raise ValueError(f"ub {tuple(ub.shape)} / ib {tuple(ib.shape)} are not [rows, {dim}]")
+    if un.numel() != ub.shape[0] or inorm.numel() != ib.shape[0]:
+        raise ValueError(f"{un.numel()} / {inorm.numel()} norms for {ub.shape[0]} / "
+                         f"{ib.shape[0]} rows")
+    if j0 < 0 or width < 1 or j0 + width > ib.shape[0]:
+        raise ValueError(f"items [{j0}, {j0 + width}) outside ib's {ib.shape[0]} rows")
     n = ub.shape[0]
     nch = -(-width // 64)
+    if out is not None:  # (a flat scratch buffer, reused across tiles; replaced when too small)
+        _typed(out, "out", torch.float32, 1)
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    if qout is not None:
+        _typed(qout, "qout", torch.uint8)
+        if qout.shape[0] != n or qout.shape[1] < -(-width // 256) * 256 \
+                or not qout.is_contiguous():
+            raise ValueError(f"qout must be contiguous [{n}, >= {-(-width // 256) * 256}], got "
+                             f"shape {tuple(qout.shape)} strides {qout.stride()}")
+    for t, name in ((un, "un"), (ib, "ib"), (inorm, "inorm"), (out, "out"), (qout, "qout")):
+        if t is not None:
+            _same_device(t, name, ub, "ub")
+    N.require_gpu(ub, "ub")
+    ub, ib, un, inorm = _aligned(ub), _aligned(ib), _aligned(un), _aligned(inorm)
     if out is None or out.numel() < n * nch:
         out = torch.empty(n * nch, dtype=torch.float32, device=ub.device)
     gb = out[:n * nch].view(n, nch)
@@ -1804,7 +1937,7 @@ class TileWalk:
         self.d = 0
         self.eu = self.ei = None
         if eu is not None:
-            self.eu, self.ei = _f32(eu, "eu"), _f32(ei, "ei")
+            self.eu, self.ei = _f32_tables(eu, ei)
             self.d = self.eu.shape[1]
             self.ub, self.un = bound_operands(self.eu)
             self.ib, self.inorm = bound_operands(self.ei)
@@ -2102,7 +2235,7 @@ def spread_rows_topk_items(rows: RowSets, W: torch.Tensor, cand: torch.Tensor, k
         excl = None  # (an empty tensor has no pointer to pass)
     d = 0
     if eu is not None:
-        eu, ei = _f32(eu, "eu"), _f32(ei, "ei")
+        eu, ei = _f32_tables(eu, ei)
         d = eu.shape[1]
         if eu.shape[0] != n or ei.shape != (I, d):
             raise ValueError("eu: one row per row of `rows`; ei: the full item table")
