@@ -479,6 +479,39 @@ int lg_spread_rows_topk_items_f64(const int64_t *user_rowptr, const int32_t *use
                                   int32_t excl_mode, int32_t k, double *out_val,
                                   int64_t *out_idx, lg_stream_t stream);
 
+/* The rank of given (row, column) targets over dense fp64 rows (csrc/rows_rank.hip K4k): where
+ * a user's held-out items stand among ALL items in the order of the spreading / LGCNHS
+ * recommendation (argsort + filter of model/SpreadMethod/recommend.py:31-50; G * F:
+ * model/SpreadLightGCN/model.py:151), at any depth. F, ldf, n_cols, eu (one row per row of F),
+ * ei, dim, the exclusion CSR (aligned with F's n_f_rows rows) and excl_mode as
+ * lg_rows_topk_f64; v(r, j) = F[r][j] or (double)G[r][j] * F[r][j], that entry's values bit
+ * for bit. A column j RANKS for row r iff v(r, j) > -inf (NaN and -inf never rank) and, under
+ * LG_EXCL_DROP, j is not in r's exclusion row. Kernel row q in [0, n_krows) names F row
+ * krow_f[q] (device, int64) and the targets t_col[t_rowptr[q] .. t_rowptr[q + 1]) (device,
+ * int64 [n_krows + 1] / int32): any order, duplicates allowed, at most LG_ROWS_RANK_ROW_MAX of
+ * them -- the caller's contract (a longer target list is several kernel rows with the same F
+ * row); the kernel clamps a longer row to the maximum and never writes out of bounds. out_rank
+ * (device, int64) and out_val (device, fp64) are aligned with t_col: for a target i of row r
+ *     out_val  = v(r, i)
+ *     out_rank = #{ ranked j != i : v(r, j) > v(r, i) || (v(r, j) == v(r, i) && j < i) }
+ *                if i ranks, else -1                                            (0 = first)
+ * so for any k <= 1024: rank < k iff lg_rows_topk_(wide_)f64's row holds i at position rank,
+ * with a bit-equal value. A target named twice gets the same rank twice. A target id outside
+ * [0, n_cols) gets {-1, -inf}, as does every target of a kernel row whose F row is outside
+ * [0, n_f_rows); an entry of t_col that belongs to no kernel row keeps what the caller put
+ * there. No workspace, no global atomics (16.5 KiB of LDS per row), integer counts: the result
+ * does not depend on how a row's columns are split over waves. LG_ERR_ARG, before any launch,
+ * on a null pointer (eu / ei and the exclusion pair may be NULL, each pair together), bad
+ * sizes, dim not in {32, 64, 128}, a bad excl_mode, a G factor with exclusions but
+ * LG_EXCL_NONE. n_krows = 0: LG_OK, nothing runs. */
+#define LG_ROWS_RANK_ROW_MAX 1024
+int lg_rows_rank_f64(const double *F, int64_t ldf, int64_t n_f_rows, int64_t n_cols,
+                     const float *eu, const float *ei, int32_t dim,
+                     const int64_t *ex_rowptr, const int32_t *ex_col, int32_t excl_mode,
+                     int64_t n_krows, const int64_t *krow_f, const int64_t *t_rowptr,
+                     const int32_t *t_col, int64_t *out_rank, double *out_val,
+                     lg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Factored spreading over item tiles: the path for catalogs whose I x I general_W / W do
  * not fit (SURVEY.md §8 a9 "K3s"; C5 = 1M x 1M would need 8 TB per matrix). The values of

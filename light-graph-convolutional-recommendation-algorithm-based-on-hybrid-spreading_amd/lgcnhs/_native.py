@@ -25,6 +25,7 @@ LG_OK = 0
 LG_ACC_NONE, LG_ACC_FIRST, LG_ACC_MID, LG_ACC_LAST, LG_ACC_ONLY = 0, 1, 2, 3, 4
 LG_EXCL_DROP, LG_EXCL_NONE = 0, 1
 LG_RANK_ROW_MAX = 4  # include/lgcnhs.h
+LG_ROWS_RANK_ROW_MAX = 1024  # include/lgcnhs.h
 ABI_VERSION = 17
 
 _vp = ctypes.c_void_p
@@ -140,6 +141,11 @@ SIGNATURES = {
     "lg_spread_rows_topk_items_f64": (
         ctypes.c_int,
         [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp,
+         _vp],
+    ),
+    "lg_rows_rank_f64": (
+        ctypes.c_int,
+        [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
          _vp],
     ),
     "lg_hybrid_recip_f64": (ctypes.c_int, [_vp, _i64, _f64, _vp, _vp, _vp]),

@@ -8,7 +8,8 @@ hamming             calHammingDistance's value, unrounded
 intra_similarity    calInternalSimilarity's value, unrounded             lg_rec_intra_similarity_f64
                     (diversity.py:66-115)
 rank_metrics        MRR, mean rank, AUC and P / R / NDCG at any cut-offs from full-catalog ranks
-                    (ops.score_rank, lg_score_rank_f32); plain torch on the ranks' device
+                    (ops.score_rank, lg_score_rank_f32; ops.spread_rank, lg_rows_rank_f64, with
+                    n_pool= for rankings that drop exclusions); plain torch on the ranks' device
 
 The reference-signature wrappers (dicts, numpy matrices, 5-decimal rounding, float32 torch
 reductions) are metrics/accurate.py and metrics/diversity.py of this package.
@@ -114,8 +115,10 @@ def intra_similarity(recs: torch.Tensor, by_item: RowSets, item_degree: torch.Te
 
 
 
-def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,)) -> dict:
-    """Ranking metrics from the full-catalog ranks of held-out items (ops.score_rank): `rank`
+def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,),
+                 n_pool: torch.Tensor | None = None) -> dict:
+    """Ranking metrics from the full-catalog ranks of held-out items (ops.score_rank,
+    ops.rows_rank, ops.spread_rank): `rank`
     int64 [nnz] aligned with targets.col (0 = first, -1 = not ranked), one row of `targets` per
     user. Plain torch on rank's device, fp64. Targets with rank -1 are left out and counted in
     n_skipped; users left with no target are not averaged. With n_t a user's evaluated targets:
@@ -124,7 +127,11 @@ def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,)) -
     mean_rank     mean over all evaluated targets of rank
     auc           mean over users of 1 - mean_i((rank_i - a_i) / (n_items - n_t)), a_i the number of
                   the user's own targets ranked above i: the share of (target, other item) pairs
-                  the model orders correctly
+                  the model orders correctly. n_pool (an int64 / fp64 [rows] tensor: the columns
+                  that rank for each user) replaces n_items in the denominator, n_pool - n_t: a
+                  ranking that DROPS a user's exclusions (ops.rows_rank, ops.spread_rank with
+                  drop=True) ranks n_items - |excl row| columns, and n_items would count the
+                  dropped ones as correctly ordered pairs. None: n_items, bit for bit as before.
     precision@k, recall@k, ndcg@k for every k in ks, from rank < k with metrics.accuracy's
                   definitions (hits / k, hits / n_t, DCG over the ideal DCG of k ones)
     n_eval        the users averaged over."""
@@ -135,6 +142,13 @@ def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,)) -
     R = targets.n_rows
     if int(rank.numel()) != int(targets.col.numel()):
         raise ValueError(f"{int(rank.numel())} ranks for {int(targets.col.numel())} targets")
+    if n_pool is not None:
+        if not isinstance(n_pool, torch.Tensor) or n_pool.dtype not in (torch.int64,
+                                                                        torch.float64):
+            raise TypeError("n_pool must be an int64 or float64 tensor")
+        if tuple(n_pool.shape) != (R,):
+            raise ValueError(f"n_pool must have shape ({R},), got {tuple(n_pool.shape)}")
+        n_pool = n_pool.to(dev, torch.float64)
     pos = torch.arange(rank.numel(), dtype=torch.int64, device=dev)
     row = torch.searchsorted(rp, pos, right=True) - 1
     inside = (row >= 0) & (row < R)
@@ -165,7 +179,7 @@ def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,)) -
     first = torch.cumsum(n_t, 0) - n_t  # the first sorted position of every user
     a = torch.empty_like(f64)
     a[order] = torch.arange(rk.numel(), dtype=torch.float64, device=dev) - first[row[order]]
-    others = (n_items - n_t).clamp(min=1.0)
+    others = ((n_items if n_pool is None else n_pool) - n_t).clamp(min=1.0)
     out["auc"] = user_mean(1.0 - zeros.index_add(0, row, (f64 - a) / others[row])
                            / n_t.clamp(min=1.0))
     gain = 1.0 / torch.log2(f64 + 2.0)

@@ -10,7 +10,9 @@ spread_resource  F = A @ W                         model/SpreadMethod/model.py:8
 rows_topk        argsort + filter + [:k], G * F    model/SpreadMethod/recommend.py:31-50,
                                                    model/SpreadLightGCN/model.py:151
                  (k <= 128: K4; 128 < k <= 1024: lists in LDS; csrc/rows_topk.hip)
-spread_topk_tiled  the above over item tiles,      (same; for catalogs whose I x I W
+rows_rank        the position of given items in    (same order, at any depth; K4k,
+spread_rank      that order, F block by block       csrc/rows_rank.hip; dense path only)
+spread_topk_tiled  the above over item tiles,     (same; for catalogs whose I x I W
                    never holding an I x I matrix    does not fit)
                    (k > 128: peeled passes of 128)
 spread_recommend   dense or tiled, whichever fits  model/SpreadMethod/recommend.py:59-115
@@ -1289,6 +1291,83 @@ def spread_topk(A: Interactions, W: torch.Tensor, k: int, excl: RowSets | None,
     return vals, idxs
 
 
+ROWS_RANK_ROW_MAX = N.LG_ROWS_RANK_ROW_MAX  # targets per kernel row (csrc/rows_rank.hip)
+
+
+def rows_rank(F: torch.Tensor, targets, excl: RowSets | None = None, drop: bool = True,
+              eu: torch.Tensor | None = None, ei: torch.Tensor | None = None, out=None):
+    """Where the given (row, column) targets stand among ALL columns of F's rows
+    (lg_rows_rank_f64): (rank int64 [nnz], value fp64 [nnz]) aligned with the target CSR's col.
+    value is v(r, i) = F[r, i], or with eu / ei the fp32 chain score promoted to fp64 times
+    F[r, i] -- rows_topk's values bit for bit. A column ranks iff its value is > -inf (NaN and
+    -inf never rank) and, with drop=True, it is not in the row's exclusions; rank is the number
+    of ranking columns before the target under (value desc, column asc), 0 = first, or -1 for
+    a target that does not rank itself. For any k <= 1024: rank < k iff rows_topk(F, k, ...)
+    holds the target at [r, rank].
+
+    targets: anything candidate_rows takes, one row per row of F. A RowSets is taken as it is:
+    its columns may come in any order, a column named twice gets the same rank twice, an
+    entry of col outside every row and a column id outside F get {-1, -inf}. Rows of any length:
+    longer than ROWS_RANK_ROW_MAX they become several kernel rows (rank_rows; no host read).
+    No targets: no launch. out: a (rank, value) pair of contiguous [nnz] tensors to write
+    into instead of fresh ones (only the entries of the targets' rows are written: callers
+    that rank F block by block over row slices of one target CSR, as spread_rank does)."""
+    _typed(F, "F", torch.float64)
+    n, m = F.shape
+    if eu is not None or ei is not None:
+        _typed(eu, "eu", torch.float32)
+        _typed(ei, "ei", torch.float32)
+        if eu.shape[0] != n or ei.shape[0] != m or eu.shape[1] != ei.shape[1]:
+            raise ValueError(f"F is {n} x {m}: eu must be [{n}, d] and ei [{m}, d], got "
+                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+    if excl is not None and excl.n_rows != n:
+        raise ValueError(f"exclusion rows {excl.n_rows} != rows of F {n}")
+    if eu is not None and excl is not None and not drop:
+        raise ValueError("a G factor with exclusions requires drop=True")
+    if isinstance(targets, RowSets) and targets.n_rows != n:
+        raise ValueError(f"target rows {targets.n_rows} != rows of F {n}")
+    N.require_gpu(F, "F")
+    dev = F.device
+    targets = candidate_rows(targets, n, m, dev)
+    if targets.col.device != dev:
+        raise ValueError(f"targets are on {targets.col.device}, F on {dev}")
+    if excl is not None and excl.col.device != dev:
+        raise ValueError(f"excl is on {excl.col.device}, F on {dev}")
+    if F.numel() and (F.stride(1) != 1 or F.data_ptr() % 16):
+        F = _aligned(F)  # (a row-strided view of a larger buffer is taken as it is)
+    d = 0
+    if eu is not None:
+        eu, ei = _f32_tables(eu, ei)
+        d = eu.shape[1]
+    if excl is not None and excl.col.numel() == 0:
+        excl = None  # (an empty tensor has no pointer to pass)
+    nnz = int(targets.col.numel())
+    if out is None:
+        rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+        val = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
+    else:
+        rank, val = out
+        _typed(rank, "out[0]", torch.int64, 1)
+        _typed(val, "out[1]", torch.float64, 1)
+        for t in (rank, val):
+            if t.numel() != nnz or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"out must be contiguous [{nnz}] tensors on {dev}")
+    if n == 0 or m == 0 or nnz == 0:
+        return rank, val
+    if nnz <= ROWS_RANK_ROW_MAX:
+        # no row can be longer than a kernel row: the target rows are the kernel rows (the
+        # request-sized call -- a few users -- is host work, and rank_rows is most of it)
+        krp, krow = targets.rowptr, torch.arange(n, dtype=torch.int64, device=dev)
+    else:
+        krp, krow = rank_rows(targets, None, row_max=ROWS_RANK_ROW_MAX)
+    N.check(N.lib().lg_rows_rank_f64(
+        N.ptr(F), F.stride(0), n, m, N.ptr(eu), N.ptr(ei), d,
+        N.ptr(excl.rowptr if excl else None), N.ptr(excl.col if excl else None),
+        N.LG_EXCL_DROP if drop else N.LG_EXCL_NONE, int(krow.numel()), N.ptr(krow), N.ptr(krp),
+        N.ptr(targets.col), N.ptr(rank), N.ptr(val), N.stream_handle(dev)), "lg_rows_rank_f64")
+    return rank, val
+
+
 # ------------------------------------------------------------------- factored spreading
 INV_TAB = 512      # degree classes cached in LDS by the walk (kInvTab, csrc/tile_lines.h)
 MAX_CLASSES = 0x7FFF   # P slot words keep bit 31 clear (it marks V entries)
@@ -2194,6 +2273,77 @@ def _spread_topk_users(A: Interactions, W: torch.Tensor, ids: torch.Tensor, k: i
                          None if eu_r is None else eu_r[b0:b1], ei)
         vals[b0:b1], idxs[b0:b1] = v, i
     return vals, idxs
+
+
+def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop: bool = True,
+                eu: torch.Tensor | None = None, ei: torch.Tensor | None = None,
+                transpose: bool = False, users=None, W: torch.Tensor | None = None,
+                tiled: bool | None = None, block_users: int | None = None):
+    """Where every user's held-out items stand among ALL items under the scores of
+    spread_recommend's dense path, (G *) A @ HybridS(A, lam): (rank int64 [nnz], value fp64
+    [nnz]) aligned with the target CSR's col, rows_rank's definitions -- for any k <= 1024,
+    rank < k iff spread_recommend(A, lam, k, excl, drop, eu, ei, ...) holds the item at
+    [row, rank], with a bit-equal value. F is computed block by block (lg_spread_resource_f64,
+    about 1 GiB of F per block, or block_users rows; the result does not depend on it) and
+    ranked by lg_rows_rank_f64; all of F is never held.
+
+    targets: anything candidate_rows takes, one row per user -- or per entry of ``users`` (ids
+    in any order, duplicates allowed), for which the interaction, exclusion and eu rows are
+    taken as spread_recommend does. ``transpose`` and ``W`` have spread_recommend's meaning.
+    tiled=True raises ValueError, as does tiled=None when dense_spread_fits says no: the
+    factored walk prunes by bounds and keeps only bounded lists, so it has no rank."""
+    dev = A.k_item.device
+    if tiled is None:
+        tiled = W is None and not dense_spread_fits(A.n_items, dev)
+    if tiled:
+        raise ValueError("spread_rank: the factored (tiled) walk keeps only bounded lists of "
+                         "every row, never a full row, and so has no rank; ranks need the "
+                         "dense path (the I x I matrices on the device, tiled=False or W=)")
+    I = A.n_items
+    if W is not None:
+        _typed(W, "W", torch.float64)
+        if tuple(W.shape) != (I, I):
+            raise ValueError(f"W has shape {tuple(W.shape)}, expected the fp64 ({I}, {I}) "
+                             f"matrix of spread_hybrid")
+    if eu is not None or ei is not None:
+        _typed(eu, "eu", torch.float32)
+        _typed(ei, "ei", torch.float32)
+        if eu.shape[0] != A.n_users or tuple(ei.shape) != (I, eu.shape[1]):
+            raise ValueError(f"eu must be [{A.n_users}, d] and ei [{I}, d], got "
+                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+    if excl is not None and excl.n_rows != A.n_users:
+        raise ValueError(f"exclusion rows {excl.n_rows} != users {A.n_users}")
+    ids = None if users is None else _user_ids(users, A.n_users, dev)
+    n = A.n_users if ids is None else int(ids.numel())
+    if isinstance(targets, RowSets) and targets.n_rows != n:
+        raise ValueError(f"target rows {targets.n_rows} != {n} users")
+    targets = candidate_rows(targets, n, I, dev)
+    nnz = int(targets.col.numel())
+    rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+    val = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
+    if n == 0 or nnz == 0:
+        return rank, val
+    if W is None:
+        W = spread_hybrid(A, lam)
+    W = _f64(W, "W")
+    rows = A.by_user if ids is None else A.by_user.take(ids)
+    ex = excl if ids is None or excl is None else excl.take(ids)
+    eu_r = eu if ids is None or eu is None else eu[ids]
+    block = max(1, min(n, (1 << 30) // max(1, I * 8))) if block_users is None \
+        else max(1, int(block_users))  # ~1 GiB of F per block
+    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=dev)
+    for b0 in range(0, n, block):
+        b1 = min(n, b0 + block)
+        Fb = buf[: b1 - b0]
+        N.check(N.lib().lg_spread_resource_f64(
+            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
+            Fb.stride(0), N.stream_handle(dev)), "lg_spread_resource_f64")
+        # the block's targets keep their absolute offsets into col: every block writes its own
+        # entries of the [nnz] outputs
+        rows_rank(Fb, targets.slice_rows(b0, b1),
+                  ex.slice_rows(b0, b1) if ex is not None else None, drop,
+                  None if eu_r is None else eu_r[b0:b1], ei, out=(rank, val))
+    return rank, val
 
 
 # ------------------------------------------------ dense spreading over a candidate item set

@@ -60,6 +60,31 @@ def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.
                                 tiled=tiled, users=users, items=items)
 
 
+def spread_lightgcn_ranks(model, user_num: int, item_num: int, train_data_df: pd.DataFrame,
+                          val_data_df: pd.DataFrame, held_df: pd.DataFrame, lambda_val: float,
+                          device=None, users=None):
+    """(targets RowSets, rank int64 [nnz]): where every held-out (user, item) of ``held_df``
+    stands among ALL items for its user under spread_lightgcn_topk's scores G * F -- the same
+    interactions, embeddings and dropped train|val items -- so rank < k iff
+    spread_lightgcn_topk(..., k) lists the item at that position of the user's row (k <= 1024;
+    the rank itself has no depth limit). rank is aligned with targets.col, 0 = first, -1 for an
+    item that does not rank. Dense path only (ops.spread_rank). ``users``: only those users'
+    rows, in that order."""
+    from model.SpreadMethod.recommend import held_out_rows
+
+    dev = device or gpu_device(model.users_emb.weight)
+    both = pd.concat([train_data_df, val_data_df])
+    inter = ops.Interactions.from_pairs(
+        torch.from_numpy(both["user_id"].to_numpy(np.int64)),
+        torch.from_numpy(both["item_id"].to_numpy(np.int64)), user_num, item_num, dev)
+    eu = model.users_emb.weight.detach().to(dev, torch.float32).contiguous()
+    ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
+    targets = held_out_rows(held_df, user_num, item_num, dev, users)
+    rank, _ = ops.spread_rank(inter, lambda_val, targets, inter.by_user, drop=True, eu=eu,
+                              ei=ei, users=users)
+    return targets, rank
+
+
 def recommendSpreadLightGCN(user_num: int, item_num: int, rating_df: pd.DataFrame,
                             train_data_df: pd.DataFrame, val_data_df: pd.DataFrame,
                             test_data_df: pd.DataFrame) -> dict:

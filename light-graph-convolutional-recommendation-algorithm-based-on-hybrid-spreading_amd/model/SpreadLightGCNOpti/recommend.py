@@ -5,7 +5,7 @@ import pandas as pd
 
 from const import cfg
 from model.SpreadLightGCN.recommend import (_save, _to_dict, recommendForAllUser,  # noqa: F401
-                                            spread_lightgcn_topk)
+                                            spread_lightgcn_ranks, spread_lightgcn_topk)
 
 
 def recommendSpreadLightGCNOpti(user_num: int, item_num: int, rating_df: pd.DataFrame,

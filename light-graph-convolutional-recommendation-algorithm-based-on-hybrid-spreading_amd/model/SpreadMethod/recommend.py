@@ -14,6 +14,7 @@ import torch
 
 from const import cfg
 from lgcnhs import ops
+from lgcnhs.graph import RowSets
 from lgcnhs.recs import topk_to_dict, exclusion_from_dfs, gpu_device, save_recs
 
 
@@ -70,6 +71,44 @@ def spread_method_topk(user_num: int, item_num: int, train_data_df: pd.DataFrame
     return ops.spread_recommend(inter, lambda_val, k, excl, drop=not unfiltered,
                                 transpose=transpose, tiled=tiled, users=users,
                                 items=items)
+
+
+def held_out_rows(held_df: pd.DataFrame, user_num: int, item_num: int, dev, users=None):
+    """The held-out positives of a DataFrame (user_id, item_id) as target rows: one sorted
+    row per user, or per entry of ``users`` in that order."""
+    held = RowSets.from_pairs(torch.from_numpy(held_df["user_id"].to_numpy(np.int64)),
+                              torch.from_numpy(held_df["item_id"].to_numpy(np.int64)),
+                              user_num, item_num, dev)
+    if users is None:
+        return held
+    return held.take(torch.as_tensor(users).to(dev, torch.int64).reshape(-1))
+
+
+def spread_method_ranks(user_num: int, item_num: int, train_data_df: pd.DataFrame,
+                        val_data_df: pd.DataFrame, held_df: pd.DataFrame, method: str,
+                        lambda_val: float, dataset: str, unfiltered: bool = False, device=None,
+                        users=None):
+    """(targets RowSets, rank int64 [nnz]): where every held-out (user, item) of ``held_df``
+    stands among ALL items for its user under spread_method_topk's scores -- the same
+    interactions, per-method overrides, exclusions and drop -- so rank < k iff
+    spread_method_topk(..., k) lists the item at that position of the user's row (k <= 1024;
+    the rank itself has no depth limit). rank is aligned with targets.col, 0 = first, -1 for an
+    item that does not rank (it is in train|val and those are dropped). Dense path only
+    (ops.spread_rank). ``users``: only those users' rows, in that order."""
+    dev = device or gpu_device()
+    both = pd.concat([train_data_df, val_data_df])
+    inter = ops.Interactions.from_pairs(
+        torch.from_numpy(both["user_id"].to_numpy(np.int64)),
+        torch.from_numpy(both["item_id"].to_numpy(np.int64)), user_num, item_num, dev)
+    transpose = False
+    if method == "ProbS" and dataset == "movielens":  # reference :87-91
+        lambda_val, transpose = 0.01, True
+    elif method == "HeatS" and dataset == "douban":  # reference :97-101
+        lambda_val, transpose = 0.99, True
+    targets = held_out_rows(held_df, user_num, item_num, dev, users)
+    rank, _ = ops.spread_rank(inter, lambda_val, targets, inter.by_user, drop=not unfiltered,
+                              transpose=transpose, users=users)
+    return targets, rank
 
 
 def recommendSpreadMethod(user_num: int, item_num: int, train_data_df: pd.DataFrame,
