@@ -653,6 +653,45 @@ int lg_spread_tile_resource_topk_f64(const int64_t *user_rowptr, const int32_t *
                                      double *io_val, int64_t *io_idx, int64_t n_positions,
                                      int64_t n_ex_positions, lg_stream_t stream);
 
+/* The tile walk with a counting finish: where the rows' targets (tgt_rowptr int64 [n_users + 1]
+ * / tgt_col int32: any order, duplicates allowed, any ids) stand among ALL columns of the F the
+ * walk sums, lg_rows_rank_f64's definitions, without ever holding a row. val and cnt are aligned
+ * with tgt_col. Two phases, each a launch per tile with lg_spread_tile_resource_topk_f64's tile,
+ * user-side and G arguments:
+ *   LG_SPREAD_RANK_VALUES  every target inside [item_begin, item_begin + width) gets
+ *       val[p] = v, the value lg_spread_tile_resource_topk_f64 would insert for that column,
+ *       bit for bit (F, or the fp32 chain score promoted to fp64 times F). gb / qb and the
+ *       exclusion arguments are not read (may be NULL). Only the tiles that hold a target need a
+ *       launch, and only the rows with a target there; entries of val whose target lies in no
+ *       tile keep the caller's value (-inf: does not rank).
+ *   LG_SPREAD_RANK_COUNTS  over ALL tiles in ascending order, after the values: cnt[p] += the
+ *       number of columns j of the tile, not dropped by the row's exclusions (ex_* and the
+ *       cursor ex_cur as in lg_spread_tile_resource_topk_f64), whose (value, item) is before
+ *       (val[p], tgt_col[p]) under (value desc, item asc). Targets whose val is NaN or -inf are
+ *       skipped. With G only columns whose bound (gb, qb) reaches the row's worst ranking val
+ *       get the exact score: a column below it is before no target. cnt starts at 0; after the
+ *       last tile it is the rank of every target that ranks (the caller drops the targets its
+ *       exclusions name). A row is owned by one wave per launch and the launches of a walk are
+ *       serialized on the stream: plain adds, no workspace, independent of the grid.
+ * Any number of targets per row: the counting runs LG_SPREAD_RANK_ROW_MAX targets per pass over
+ * the row's tile in LDS. Never allocates; sizes and limits as lg_spread_tile_resource_topk_f64. */
+#define LG_SPREAD_RANK_ROW_MAX 8
+#define LG_SPREAD_RANK_VALUES 0
+#define LG_SPREAD_RANK_COUNTS 1
+int lg_spread_tile_resource_rank_f64(const int64_t *user_rowptr, const int32_t *user_items,
+                                     const double *ra_edge, int64_t n_users,
+                                     const void *lines, const void *ovf, int32_t null_row,
+                                     const double *rbeta,
+                                     const double *inv_cls, int32_t item_begin, int32_t tile,
+                                     int32_t width, const float *eu, const float *ei,
+                                     int32_t dim, const float *gb, int32_t n_chunks,
+                                     const uint8_t *qb, int32_t qstride,
+                                     const int64_t *ex_rowptr, const int32_t *ex_col,
+                                     int64_t *ex_cur, const int64_t *tgt_rowptr,
+                                     const int32_t *tgt_col, int32_t phase, double *val,
+                                     int64_t *cnt, int64_t n_positions, int64_t n_ex_positions,
+                                     lg_stream_t stream);
+
 /* x_bf16[r] = bf16(x[r]) (round to nearest even), norm_up[r] = ||x[r]||_2 rounded up to
  * fp32: the operands of lg_score_chunk_bound (csrc/gbound.hip). err_up (optional, may be
  * NULL): err_up[r] = ||x[r] - x_bf16[r]||_2 rounded up, the rounding-error norms the

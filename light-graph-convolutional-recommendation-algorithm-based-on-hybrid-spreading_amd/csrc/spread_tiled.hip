@@ -30,7 +30,18 @@ namespace lg {
 //            score chain from lg_score_chunk_bound (bf16 MFMA + a rigorous rounding margin):
 //            only those columns get rb_j and (with G) the exact chain score. Ids grow along
 //            the walk, so "beats" is v > tau (a tie loses to the older, smaller id).
-constexpr int MODE_F = 0, MODE_TOPK = 1;
+// MODE_RANK: where given targets stand among all columns (lg_spread_tile_resource_rank_f64),
+//            in two phases. Value phase: v of the user's targets inside the tile -- MODE_TOPK's
+//            value of that column, bit for bit -- goes to val[position in tgt_col]. Count phase:
+//            the tile's columns become their values in place in acc (excluded and screened-out
+//            columns -inf), then every target's count of columns before it under (value desc,
+//            item asc) is added to cnt[position], kRankPass targets per pass over acc, per-lane
+//            counters reduced once per pass. With G a column gets the exact chain score only if
+//            its bound (MODE_TOPK's two tests, with >= : an equal value with a smaller id is
+//            before the target) reaches tau = the user's worst ranking target value, which never
+//            moves; a column below it is before no target.
+constexpr int MODE_F = 0, MODE_TOPK = 1, MODE_RANK = 2;
+constexpr int kRankPass = LG_SPREAD_RANK_ROW_MAX;  // targets per counting pass over acc
 constexpr int kWalkQ = 8;       // line loads per lane per batch: 8 rows each, 64 rows
 constexpr int kBatchRows = 8 * kWalkQ;
 // per-wave scratch list: the batch's overflow rows during the decode, the exact-score queue
@@ -70,6 +81,12 @@ struct WalkArgs {
   int k, first;
   double *io_val;
   int64_t *io_idx;
+  // MODE_RANK (with the G and exclusion fields above)
+  const int64_t *tgt_rowptr;  // the rows' targets, any order, any ids
+  const int32_t *tgt_col;
+  int phase;                  // 0: values, 1: counts
+  double *val;                // aligned with tgt_col: written by phase 0, read by phase 1
+  int64_t *cnt;               // aligned with tgt_col: phase 1 adds the tile's counts
 };
 
 // accumulator columns per wave: the tile rounded up to whole 512-column scan steps
@@ -158,6 +175,27 @@ __device__ __forceinline__ void add_slot_fast(double *acc, uint32_t s, double ra
   if (s) lds_add(acc, s & 0xFFFFu, inv * ra);
 }
 
+// The exact fp32 scores of 16 columns against one user row: column m = lane % 16 as A row m
+// (ir: its item row + (lane / 16) D / 4), the user row as every B column (ur likewise). The
+// per-element sums are the fp32 chain acc = fmaf(u[g*D/4+s], i[g*D/4+s], acc) (s outer, g
+// inner) of lg_score_topk_f32; column mm's sum: lane 16 (mm / 4), element mm % 4.
+template <int D>
+__device__ __forceinline__ f32x4 chain_mfma16(const float *ir, const float *ur) {
+  constexpr int Qd = D / 4;              // MFMA steps
+  constexpr int H = Qd < 16 ? Qd : 16;   // steps per load round (<= 16 VGPRs each)
+  f32x4 sc4 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int h0 = 0; h0 < Qd; h0 += H) {
+    float av[H], bv[H];
+    load_piece<H>(ir + h0, av);
+    load_piece<H>(ur + h0, bv);
+#pragma unroll
+    for (int s = 0; s < H; ++s)
+      sc4 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], sc4, 0, 0, 0);
+  }
+  return sc4;
+}
+
 // A batch of the wave's stream: rows [r0, r1) of user u (whose rows end at e); xc / xh =
 // the user's exclusion cursor and row end (prefetched with its row pointers). 32-bit fields
 // (the host requires users, interactions and exclusions < 2^31): the stream state then fits
@@ -222,7 +260,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
   if (lane == 0) s_red[wave] = rmax;
   for (int j = lane; j < acc_cols(tile); j += 64) acc[j] = 0.0;
   __syncthreads();
-  if (MODE == MODE_TOPK && D > 0) {
+  if (MODE != MODE_F && D > 0) {
     for (int c = wave; 64 * c < tile && c < 64; c += nw) {
       double m = s_rb[64 * c + lane < tile ? 64 * c + lane : 0];
 #pragma unroll
@@ -249,7 +287,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
   // (clamped past the last user; the same address until a user starts): a load issued only
   // when a user starts leaves a register copy at the join, which hipcc also guards with
   // vmcnt(0).
-  const bool has_ex = MODE == MODE_TOPK && a.ex_rowptr != nullptr;
+  const bool has_ex = MODE != MODE_F && a.ex_rowptr != nullptr;
   int32_t uq = (int32_t)u_first;
   int32_t pr = 0, px = 0;  // lanes 0, 1: the prefetched (start, end) / (cursor, end)
   // (positions < 2^31: the low dword of each int64 entry, one 4-byte load -- a whole int64
@@ -321,7 +359,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
   // is issued (clamped user, 0-byte descriptors for absent operands), the consumers apply the
   // masks at the finish
   constexpr bool kTwo = M > 2;  // k > 64: the list spans two registers per lane
-  const bool has_qb = MODE == MODE_TOPK && D > 0 && a.qb != nullptr;
+  const bool has_qb = MODE != MODE_F && D > 0 && a.qb != nullptr;
   auto load_state = [&](const Batch &x, UState &st) __attribute__((always_inline)) {
     if constexpr (MODE == MODE_TOPK) {
       const int k = a.k;
@@ -467,7 +505,28 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
     }
   };
 
-  // ---- the user's tile of F: written out (MODE_F) or merged into its top-K list
+  // excluded items of this tile (the next run of the user's sorted exclusion row, from the
+  // user's cursor; xw0 = its first 64 entries, one per lane): acc = -inf, the cursor moves on
+  auto mark_excluded = [&](const Batch &x, int32_t xw0) __attribute__((always_inline)) {
+    int64_t xpos = x.xc;
+    const int64_t xhi = x.xh;
+    int32_t xw = has_ex && xpos + lane < xhi ? xw0 : 0x7fffffff;
+    const int32_t lim = a.item_begin + a.width;
+    if (has_ex) {
+      for (;;) {
+        const bool in = xw < lim;
+        if (in && xw >= a.item_begin) acc[xw - a.item_begin] = neg_inf<double>();
+        const int nin = __popcll(__ballot(in));
+        xpos += nin;
+        if (nin < 64) break;
+        xw = xpos + lane < xhi ? a.ex_col[xpos + lane] : 0x7fffffff;  // > 64 in one tile
+      }
+      if (lane == 0) a.ex_cur[x.u] = xpos;
+    }
+  };
+
+  // ---- the user's tile of F: written out (MODE_F), merged into its top-K list (MODE_TOPK)
+  // or ranked against (MODE_RANK)
   auto finish_user = [&](const Batch &x, UState &st) __attribute__((always_inline)) {
     const int64_t u = x.u;
     wave_sync();
@@ -485,6 +544,224 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
         __builtin_nontemporal_store(acc[j] * s_rb[j], row + j);
         acc[j] = 0.0;
       }
+    } else if constexpr (MODE == MODE_RANK) {
+      // the user's targets: positions [tb, te) of tgt_col; val and cnt are aligned with it
+      const int64_t tb = a.tgt_rowptr[u], te = a.tgt_rowptr[u + 1];
+      const int wend = (a.width + 511) & ~511;  // acc is used in whole 512-column steps
+      auto zero_acc = [&]() __attribute__((always_inline)) {
+        for (int j = 2 * lane; j < wend; j += 128)
+          *reinterpret_cast<double2 *>(acc + j) = double2{0.0, 0.0};
+        wave_sync();
+      };
+      if (a.phase == 0) {
+        // ---- values: 16 targets per round, target m of the round in the lanes with
+        // lane % 16 = m (the MFMA batch's A rows); MODE_TOPK's v = (double)score * (acc * rb)
+        const int m = lane & 15;
+        for (int64_t p0 = tb; p0 < te; p0 += 16) {
+          const int64_t p = p0 + m;
+          const int64_t c = (p < te ? (int64_t)a.tgt_col[p] : -1) - a.item_begin;
+          const bool in = p < te && c >= 0 && c < a.width;
+          if (!__ballot(in)) continue;  // (uniform)
+          const int cc = in ? (int)c : 0;
+          const double f = acc[cc] * s_rb[cc];
+          double v = f;
+          if constexpr (D > 0) {
+            const int g = lane >> 4;
+            const f32x4 sc4 = chain_mfma16<D>(a.ei + (int64_t)(a.item_begin + cc) * D + g * (D / 4),
+                                              a.eu + u * D + g * (D / 4));
+            const int src = 16 * (m >> 2);  // target m's sum: lane 16 (m / 4), element m % 4
+            const float e0 = __shfl(sc4[0], src), e1 = __shfl(sc4[1], src);
+            const float e2 = __shfl(sc4[2], src), e3 = __shfl(sc4[3], src);
+            const float sc = (m & 3) == 0 ? e0 : (m & 3) == 1 ? e1 : (m & 3) == 2 ? e2 : e3;
+            v = (double)sc * f;
+          }
+          if (in && lane < 16) a.val[p] = v;
+        }
+        zero_acc();
+        return;
+      }
+      // ---- counts
+      mark_excluded(x, x.xc + lane < x.xh ? a.ex_col[x.xc + lane] : 0x7fffffff);
+      wave_sync();
+      // tau: the worst ranking target value (a target ranks iff its value is > -inf)
+      double tau = __builtin_huge_val();
+      uint64_t live = 0;
+      for (int64_t p0 = tb; p0 < te; p0 += 64) {
+        const double v = p0 + lane < te ? a.val[p0 + lane] : neg_inf<double>();
+        const bool r = v > neg_inf<double>();
+        live |= __ballot(r);
+        tau = r && v < tau ? v : tau;
+      }
+      if (!live) {  // nothing to count (no target, or none that ranks)
+        zero_acc();
+        return;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double t2 = __shfl_xor(tau, o);
+        tau = t2 < tau ? t2 : tau;
+      }
+      // step 1: acc[j] becomes column j's value, -inf for excluded columns, columns past the
+      // width and (G) columns whose bound is below tau
+      if constexpr (D == 0) {
+        for (int j = 2 * lane; j < wend; j += 128) {
+          double2 y = *reinterpret_cast<const double2 *>(acc + j);
+          y.x = j < a.width ? y.x * s_rb[j < a.width ? j : 0] : neg_inf<double>();
+          y.y = j + 1 < a.width ? y.y * s_rb[j + 1 < a.width ? j + 1 : 0] : neg_inf<double>();
+          *reinterpret_cast<double2 *>(acc + j) = y;
+        }
+      } else {
+        int ncand = 0;
+        double *cq_f = ovl_ra;     // queued f (the decode's overflow list, free here)
+        uint32_t *cq_j = ovl_ent;  // queued column
+        // the queued columns' exact values into acc (MODE_TOPK's flush, stored not inserted)
+        auto score_queue = [&]() __attribute__((always_inline)) {
+          wave_sync();
+          const int m = lane & 15, g = lane >> 4;
+          for (int b0 = 0; b0 < ncand; b0 += 16) {
+            const int nb = ncand - b0 < 16 ? ncand - b0 : 16;
+            const int ci = b0 + (m < nb ? m : 0);
+            const f32x4 sc4 = chain_mfma16<D>(
+                a.ei + (int64_t)(a.item_begin + (int)cq_j[ci]) * D + g * (D / 4),
+                a.eu + u * D + g * (D / 4));
+            if (m == 0) {  // candidates 4 g .. 4 g + 3: this lane's four sums
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const int mm = 4 * g + e;
+                const float sc = e == 0 ? sc4[0] : e == 1 ? sc4[1] : e == 2 ? sc4[2] : sc4[3];
+                if (mm < nb) acc[cq_j[b0 + mm]] = (double)sc * cq_f[b0 + mm];
+              }
+            }
+          }
+          ncand = 0;
+          wave_sync();
+        };
+        // MODE_TOPK's screen scales, per 64-column chunk c in lane c
+        const double gp = (double)fmaxf(a.gb[u * a.nch + (lane < a.nch ? lane : 0)], 0.f);
+        const double sc_v = s_rbc[lane < a.nch ? lane : 0] * (1.0 + 0x1p-50) * gp * (1.0 / 255.0);
+        const double bq_v = gp * (1.0 / 255.0) * (1.0 + 0x1p-50);
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+            has_qb ? (void *)(a.qb + u * a.qstride) : (void *)a.lines, 0,
+            has_qb ? a.qstride : 0, 0x00020000);
+        const double2 ninf2{neg_inf<double>(), neg_inf<double>()};
+        for (int c0 = 0; c0 < a.width; c0 += 512) {
+          // the 8-bit bounds of the lane's columns (without qb: 255, the chunk bound alone)
+          uint32_t qa = 0xFFFFFFFFu, qb2 = 0xFFFFFFFFu;
+          if (has_qb) {  // (uniform; range-checked against qstride)
+            qa = __builtin_amdgcn_raw_buffer_load_b32(rq, (uint32_t)(4 * lane + c0), 0, 0);
+            qb2 = __builtin_amdgcn_raw_buffer_load_b32(rq, (uint32_t)(4 * lane + c0 + 256), 0, 0);
+          }
+          double sv[8];
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+            for (int pp = 0; pp < 2; ++pp) {
+              const int j = c0 + 256 * hh + 4 * lane + 2 * pp;
+              const double2 y = *reinterpret_cast<const double2 *>(acc + j);
+              *reinterpret_cast<double2 *>(acc + j) = ninf2;
+              sv[4 * hh + 2 * pp] = y.x;
+              sv[4 * hh + 2 * pp + 1] = y.y;
+            }
+          if (c0 + 512 > a.width) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+              const int j = c0 + 256 * (t >> 2) + 4 * lane + (t & 3);
+              if (j >= a.width) sv[t] = neg_inf<double>();
+            }
+          }
+          const double sc0 = __shfl(sc_v, ((c0 + 4 * lane) >> 6) & 63);
+          const double sc1 = __shfl(sc_v, ((c0 + 256 + 4 * lane) >> 6) & 63);
+          uint32_t mask = 0;
+#pragma unroll
+          for (int t = 0; t < 8; ++t) {  // (excluded: b = -inf or NaN, never taken)
+            const uint32_t qq = t < 4 ? qa : qb2;
+            const double qv = (double)((qq >> (8 * (t & 3))) & 0xFFu);
+            const double b = sv[t] * qv * (t < 4 ? sc0 : sc1);
+            mask |= b >= tau ? 1u << t : 0u;
+          }
+          while (__ballot(mask != 0)) {
+            const bool has = mask != 0;
+            const int t = has ? __ffs(mask) - 1 : 0;
+            mask &= mask - 1;
+            double s = sv[0];
+#pragma unroll
+            for (int y = 1; y < 8; ++y) s = t == y ? sv[y] : s;
+            const int j = c0 + 256 * (t >> 2) + 4 * lane + (t & 3);
+            const double f = has ? s * s_rb[has ? j : 0] : -1.0;
+            const uint32_t qq = t < 4 ? qa : qb2;
+            const double bq = (double)((qq >> (8 * (t & 3))) & 0xFFu) *
+                              __shfl(bq_v, (j >> 6) & 63);
+            const bool cand = has && bq * f >= tau;
+            const uint64_t bal = __ballot(cand);
+            if (bal) {
+              const int nb = __popcll(bal);
+              if (ncand + nb > kOvfList) score_queue();  // (nb <= 64 <= kOvfList)
+              if (cand) {
+                const int p = ncand + __popcll(bal & lanemask_lt());
+                cq_f[p] = f;
+                cq_j[p] = (uint32_t)j;
+              }
+              ncand += nb;
+              if (ncand >= 16) score_queue();
+            }
+          }
+        }
+        if (ncand) score_queue();
+      }
+      wave_sync();
+      // step 2: kRankPass targets per pass over acc, per-lane counters reduced once per pass;
+      // a target that does not rank compares as NaN (before nothing, after nothing)
+      for (int64_t p0 = tb; p0 < te; p0 += kRankPass) {
+        const int np = (int)(te - p0 < kRankPass ? te - p0 : kRankPass);
+        double tvl = __builtin_nan("");
+        int til = 0;
+        if (lane < np) {
+          const double v = a.val[p0 + lane];
+          tvl = v > neg_inf<double>() ? v : tvl;
+          til = a.tgt_col[p0 + lane];
+        }
+        if (!__ballot(tvl == tvl)) continue;  // (uniform)
+        int64_t mine = 0;
+        if (np == 1) {  // leave-one-out: one compare per column
+          const double tv = __shfl(tvl, 0);
+          const int ti = __shfl(til, 0);
+          int c = 0;
+          for (int j = 2 * lane; j < wend; j += 128) {
+            const double2 y = *reinterpret_cast<const double2 *>(acc + j);
+            c += before(y.x, a.item_begin + j, tv, ti) ? 1 : 0;
+            c += before(y.y, a.item_begin + j + 1, tv, ti) ? 1 : 0;
+          }
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+          mine = c;
+        } else {
+          double tv[kRankPass];
+          int ti[kRankPass], c[kRankPass];
+#pragma unroll
+          for (int i = 0; i < kRankPass; ++i) {
+            tv[i] = __shfl(tvl, i);
+            ti[i] = __shfl(til, i);
+            c[i] = 0;
+          }
+          for (int j = 2 * lane; j < wend; j += 128) {
+            const double2 y = *reinterpret_cast<const double2 *>(acc + j);
+#pragma unroll
+            for (int i = 0; i < kRankPass; ++i) {
+              c[i] += before(y.x, a.item_begin + j, tv[i], ti[i]) ? 1 : 0;
+              c[i] += before(y.y, a.item_begin + j + 1, tv[i], ti[i]) ? 1 : 0;
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < kRankPass; ++i) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) c[i] += __shfl_xor(c[i], o);
+            mine = lane == i ? c[i] : mine;
+          }
+        }
+        // one wave owns the user in every launch of the walk: a plain load-add-store
+        if (lane < np && tvl == tvl) a.cnt[p0 + lane] += mine;
+      }
+      zero_acc();
     } else {
       const int k = a.k;
       // the running list in registers: entry lane (L0, I0) and 64 + lane (L1, I1), sorted by
@@ -505,9 +782,6 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
 #pragma unroll
         for (int kk = 0; kk < kQPre; ++kk) qr[kk] = 0xFFFFFFFFu;
       }
-      int64_t xpos = x.xc;
-      const int64_t xhi = x.xh;
-      int32_t xw = has_ex && xpos + lane < xhi ? st.xw : 0x7fffffff;
       auto kth = [&](double &tv, int &ti) __attribute__((always_inline)) {
         if (!kTwo || k <= 64) {
           tv = __shfl(L0, k - 1);
@@ -546,19 +820,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
         if (lane >= k) { L0 = neg_inf<double>(); I0 = kPadId; }
         kth(tau, tau_id);
       };
-      // excluded items of this tile (the next run of the user's sorted exclusion row): -1
-      const int32_t lim = a.item_begin + a.width;
-      if (has_ex) {
-        for (;;) {
-          const bool in = xw < lim;
-          if (in && xw >= a.item_begin) acc[xw - a.item_begin] = neg_inf<double>();
-          const int nin = __popcll(__ballot(in));
-          xpos += nin;
-          if (nin < 64) break;
-          xw = xpos + lane < xhi ? a.ex_col[xpos + lane] : 0x7fffffff;  // > 64 in one tile
-        }
-        if (lane == 0) a.ex_cur[u] = xpos;
-      }
+      mark_excluded(x, st.xw);
       wave_sync();
       // The scan: lane l reads columns c0 + 2l, c0 + 2l + 1 (ds_read_b128), 4 reads in flight
       // (512 columns). A column can enter only if acc > thr, thr = tau / (rb_max (1 + 2^-50)
@@ -587,8 +849,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
         }
 #endif
         if constexpr (D > 0) {
-          constexpr int Qd = D / 4;              // MFMA steps
-          constexpr int H = Qd < 16 ? Qd : 16;   // steps per load round (<= 16 VGPRs each)
+          constexpr int Qd = D / 4;
           wave_sync();
           const int m = lane & 15, g = lane >> 4;
           for (int b0 = 0; b0 < ncand; b0 += 16) {
@@ -596,16 +857,7 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
             const int ci = b0 + (m < nb ? m : 0);
             const float *ir = a.ei + (int64_t)(a.item_begin + (int)cq_j[ci]) * D + g * Qd;
             const float *ur = a.eu + u * D + g * Qd;
-            f32x4 sc4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int h0 = 0; h0 < Qd; h0 += H) {
-              float av[H], bv[H];
-              load_piece<H>(ir + h0, av);
-              load_piece<H>(ur + h0, bv);
-#pragma unroll
-              for (int s = 0; s < H; ++s)
-                sc4 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], sc4, 0, 0, 0);
-            }
+            const f32x4 sc4 = chain_mfma16<D>(ir, ur);
             // candidate mm's sum: lane 16 (mm / 4), element mm % 4
             for (int mm = 0; mm < nb; ++mm) {
               const float e = (mm & 3) == 0 ? sc4[0] : (mm & 3) == 1 ? sc4[1]
@@ -799,7 +1051,11 @@ __global__ __launch_bounds__(512) void k_tile_walk(WalkArgs a) {
             const uint32_t qq = t < 4 ? qa : qb2;
             const double bq = (double)((qq >> (8 * (t & 3))) & 0xFFu) *
                               __shfl(bq_v, (j >> 6) & 63);
-            const bool cand = has && bq * f > tau;
+            // (>=: tau moves while this step's columns are drained -- its mask was taken at
+            // the step's start -- so a column of the step that ties the new k-th value may
+            // still have the smaller id; insert1 decides by (value, id). Columns of later
+            // steps and tiles have larger ids: their strict mask test stands.)
+            const bool cand = has && bq * f >= tau;
             const uint64_t bal = __ballot(cand);
             if (bal) {
               const int nb = __popcll(bal);
@@ -914,7 +1170,7 @@ static int launch_walk(const WalkArgs &a, hipStream_t s) {
   const unsigned blocks = (unsigned)(want < cap ? want : cap);
   const size_t lds = shared + (size_t)nw * per;
   bool seeded = false;
-  if constexpr (D > 0 && M <= 2) {  // (the seeded finish: k <= 64 with a G factor)
+  if constexpr (MODE == MODE_TOPK && D > 0 && M <= 2) {  // (the seeded finish: k <= 64 with G)
     if (a.first) {
       k_tile_walk<MODE, D, M, true><<<dim3(blocks), dim3(64 * nw), lds, s>>>(a);
       seeded = true;
@@ -1011,4 +1267,87 @@ extern "C" int lg_spread_tile_resource_topk_f64(
   }
   if (st != LG_OK) return st;
   return launch_status("lg_spread_tile_resource_topk_f64");
+}
+
+extern "C" int lg_spread_tile_resource_rank_f64(
+    const int64_t *user_rowptr, const int32_t *user_items, const double *ra_edge,
+    int64_t n_users, const void *lines, const void *ovf, int32_t null_row, const double *rbeta,
+    const double *inv_cls, int32_t item_begin, int32_t tile, int32_t width, const float *eu,
+    const float *ei, int32_t dim, const float *gb, int32_t n_chunks, const uint8_t *qb,
+    int32_t qstride, const int64_t *ex_rowptr, const int32_t *ex_col, int64_t *ex_cur,
+    const int64_t *tgt_rowptr, const int32_t *tgt_col, int32_t phase, double *val, int64_t *cnt,
+    int64_t n_positions, int64_t n_ex_positions, lg_stream_t stream) {
+  const char *who = "lg_spread_tile_resource_rank_f64";
+  LG_REQUIRE(user_rowptr && user_items && ra_edge && lines && ovf && rbeta && inv_cls &&
+                 tgt_rowptr && tgt_col && val && n_users >= 0 && n_users < 0x7fffffff &&
+                 item_begin >= 0,
+             "%s: bad arguments", who);
+  LG_REQUIRE(phase == LG_SPREAD_RANK_VALUES || phase == LG_SPREAD_RANK_COUNTS,
+             "%s: phase %d is neither LG_SPREAD_RANK_VALUES nor LG_SPREAD_RANK_COUNTS", who,
+             phase);
+  LG_REQUIRE(phase == LG_SPREAD_RANK_VALUES || cnt, "%s: the count phase needs cnt", who);
+  // (the walk's stream positions are 32-bit)
+  LG_REQUIRE(n_positions >= 0 && n_positions < 0x7fffffff && n_ex_positions >= 0 &&
+                 n_ex_positions < 0x7fffffff,
+             "%s: %lld interactions / %lld exclusions exceed the walk's 32-bit positions", who,
+             (long long)n_positions, (long long)n_ex_positions);
+  LG_REQUIRE(tile >= 1 && tile <= 8192 && width >= 1 && width <= tile &&
+                 (int64_t)item_begin + width < 0x7fffffff,
+             "%s: tile %d / width %d", who, tile, width);
+  LG_REQUIRE(!eu == !ei, "%s: eu and ei go together", who);
+  // (the value phase screens nothing: gb is read by the count phase only)
+  LG_REQUIRE(eu ? (phase == LG_SPREAD_RANK_VALUES || gb) : !gb,
+             "%s: gb goes with eu and ei (the count phase needs it)", who);
+  LG_REQUIRE(!eu || dim == 32 || dim == 64 || dim == 128, "%s: dim %d not in {32,64,128}", who,
+             dim);
+  LG_REQUIRE(!gb || n_chunks == (width + 63) / 64, "%s: n_chunks %d != ceil(width / 64)", who,
+             n_chunks);
+  LG_REQUIRE(!qb || (gb && qstride >= (width + 255) / 256 * 256),
+             "%s: qb needs gb and qstride >= width rounded to 256", who);
+  LG_REQUIRE(!eu || width <= 4096,
+             "%s: a G factor needs width <= 4096 (one chunk bound per lane), got %d", who, width);
+  LG_REQUIRE(!ex_rowptr == !ex_col && !ex_rowptr == !ex_cur,
+             "%s: ex_rowptr/ex_col/ex_cur go together", who);
+  LG_REQUIRE(null_row >= 0 && null_row < (1 << 25) - 1,
+             "tile walk: %d items exceed the 32-bit line offsets", null_row);
+  if (n_users == 0) return LG_OK;
+  WalkArgs a{};
+  a.user_rowptr = user_rowptr;
+  a.user_items = user_items;
+  a.ra_edge = ra_edge;
+  a.n_users = n_users;
+  a.lines = (const uint4 *)lines;
+  a.ovf = (const uint4 *)ovf;
+  a.null_row = null_row;
+  a.item_begin = item_begin;
+  a.tile = tile;
+  a.width = width;
+  a.rbeta = rbeta;
+  a.g_inv = inv_cls;
+  a.eu = eu;
+  a.ei = ei;
+  a.gb = gb;
+  a.nch = n_chunks;
+  a.qb = qb;
+  a.qstride = qstride;
+  // (exclusions drop columns from the counts; the values are those of the columns themselves)
+  const bool counts = phase == LG_SPREAD_RANK_COUNTS;
+  a.ex_rowptr = counts ? ex_rowptr : nullptr;
+  a.ex_col = counts ? ex_col : nullptr;
+  a.ex_cur = counts ? ex_cur : nullptr;
+  a.tgt_rowptr = tgt_rowptr;
+  a.tgt_col = tgt_col;
+  a.phase = counts ? 1 : 0;
+  a.val = val;
+  a.cnt = cnt;
+  hipStream_t s = (hipStream_t)stream;
+  int st;
+  switch (eu ? dim : 0) {
+    case 0: st = launch_walk<MODE_RANK, 0, 2>(a, s); break;
+    case 32: st = launch_walk<MODE_RANK, 32, 2>(a, s); break;
+    case 64: st = launch_walk<MODE_RANK, 64, 2>(a, s); break;
+    default: st = launch_walk<MODE_RANK, 128, 2>(a, s); break;
+  }
+  if (st != LG_OK) return st;
+  return launch_status(who);
 }

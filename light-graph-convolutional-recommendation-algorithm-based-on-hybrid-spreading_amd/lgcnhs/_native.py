@@ -26,6 +26,8 @@ LG_ACC_NONE, LG_ACC_FIRST, LG_ACC_MID, LG_ACC_LAST, LG_ACC_ONLY = 0, 1, 2, 3, 4
 LG_EXCL_DROP, LG_EXCL_NONE = 0, 1
 LG_RANK_ROW_MAX = 4  # include/lgcnhs.h
 LG_ROWS_RANK_ROW_MAX = 1024  # include/lgcnhs.h
+LG_SPREAD_RANK_ROW_MAX = 8  # include/lgcnhs.h
+LG_SPREAD_RANK_VALUES, LG_SPREAD_RANK_COUNTS = 0, 1
 ABI_VERSION = 17
 
 _vp = ctypes.c_void_p
@@ -168,6 +170,10 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
          _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp]),
+    "lg_spread_tile_resource_rank_f64": (
+        ctypes.c_int,
+        [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
+         _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp]),
     "lg_bound_prep_f32": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "lg_score_chunk_bound": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp,
                                             _vp, _i32, _vp]),

@@ -118,7 +118,8 @@ def intra_similarity(recs: torch.Tensor, by_item: RowSets, item_degree: torch.Te
 def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,),
                  n_pool: torch.Tensor | None = None) -> dict:
     """Ranking metrics from the full-catalog ranks of held-out items (ops.score_rank,
-    ops.rows_rank, ops.spread_rank): `rank`
+    ops.rows_rank, ops.spread_rank, or ops.spread_rank_tiled where the dense spreading
+    matrices do not fit): `rank`
     int64 [nnz] aligned with targets.col (0 = first, -1 = not ranked), one row of `targets` per
     user. Plain torch on rank's device, fp64. Targets with rank -1 are left out and counted in
     n_skipped; users left with no target are not averaged. With n_t a user's evaluated targets:
@@ -129,8 +130,8 @@ def rank_metrics(rank: torch.Tensor, targets: RowSets, n_items: int, ks=(20,),
                   the user's own targets ranked above i: the share of (target, other item) pairs
                   the model orders correctly. n_pool (an int64 / fp64 [rows] tensor: the columns
                   that rank for each user) replaces n_items in the denominator, n_pool - n_t: a
-                  ranking that DROPS a user's exclusions (ops.rows_rank, ops.spread_rank with
-                  drop=True) ranks n_items - |excl row| columns, and n_items would count the
+                  ranking that DROPS a user's exclusions (ops.rows_rank, ops.spread_rank,
+                  ops.spread_rank_tiled with drop=True) ranks n_items - |excl row| columns, and n_items would count the
                   dropped ones as correctly ordered pairs. None: n_items, bit for bit as before.
     precision@k, recall@k, ndcg@k for every k in ks, from rank < k with metrics.accuracy's
                   definitions (hits / k, hits / n_t, DCG over the ideal DCG of k ones)

@@ -2060,6 +2060,37 @@ class TileWalk:
         return chunk_bounds(self.ub, self.un, self.ib, self.inorm, self.d, j0, width,
                             self.gbuf, self.qbuf)
 
+    def _user_side(self, scale: HybridScale):
+        """(rowptr, items, ra per interaction) of the walk's rows: A's own, or the taken rows."""
+        if self.rows is None:
+            return self.A.by_user.rowptr[self.u0:], self.A.by_user.col, scale.ra_edge
+        if self._ra[0] is not scale:  # (one gather per lambda, not per tile)
+            self._ra = (scale, torch.cat([scale.ra_edge[self.edge_src],
+                                          scale.ra_edge.new_zeros(1)]))
+        return self.rows.rowptr, self.rows.col, self._ra[1]
+
+    def count_step(self, lines, ovf, inv_cls, scale: HybridScale, j0: int, tile: int,
+                   width: int, targets: RowSets, val: torch.Tensor, cnt: torch.Tensor,
+                   bnd=None) -> None:
+        """The count phase of lg_spread_tile_resource_rank_f64 for tile [j0, j0 + width): adds
+        to cnt, for every target of the walk's rows, the tile's columns before it (val: the
+        targets' values, from the value phase). Tiles in ascending order, as step()."""
+        ex = self.ex
+        if self.d and bnd is None:
+            bnd = self.bounds(j0, width, scale)
+        gb, q = bnd if bnd is not None else (None, None)
+        u_rowptr, u_col, ra_edge = self._user_side(scale)
+        N.check(N.lib().lg_spread_tile_resource_rank_f64(
+            N.ptr(u_rowptr), N.ptr(u_col), N.ptr(ra_edge), self.n, N.ptr(lines), N.ptr(ovf),
+            self.A.n_items, N.ptr(scale.rb), N.ptr(inv_cls), int(j0), int(tile), int(width),
+            N.ptr(self.eu), N.ptr(self.ei), self.d, N.ptr(gb),
+            gb.shape[1] if gb is not None else 0, N.ptr(q), 0 if q is None else q.shape[1],
+            N.ptr(ex.rowptr if ex is not None else None),
+            N.ptr(ex.col if ex is not None else None), N.ptr(self.ex_cur),
+            N.ptr(targets.rowptr), N.ptr(targets.col), N.LG_SPREAD_RANK_COUNTS, N.ptr(val),
+            N.ptr(cnt), u_col.numel(), ex.col.numel() if ex is not None else 0,
+            N.stream_handle(self.dev)), "lg_spread_tile_resource_rank_f64")
+
     def step(self, lines, ovf, inv_cls, scale: HybridScale, j0: int, tile: int, width: int,
              first: bool, bnd=None) -> None:
         """Merge tile [j0, j0 + width) (its rows: lines / ovf) into the lists; bnd = the
@@ -2069,13 +2100,7 @@ class TileWalk:
             bnd = self.bounds(j0, width, scale)
         gb, q = bnd if bnd is not None else (None, None)
         nch = gb.shape[1] if gb is not None else 0
-        if self.rows is None:
-            u_rowptr, u_col, ra_edge = A.by_user.rowptr[self.u0:], A.by_user.col, scale.ra_edge
-        else:
-            if self._ra[0] is not scale:  # (one gather per lambda, not per tile)
-                self._ra = (scale, torch.cat([scale.ra_edge[self.edge_src],
-                                              scale.ra_edge.new_zeros(1)]))
-            u_rowptr, u_col, ra_edge = self.rows.rowptr, self.rows.col, self._ra[1]
+        u_rowptr, u_col, ra_edge = self._user_side(scale)
         N.check(N.lib().lg_spread_tile_resource_topk_f64(
             N.ptr(u_rowptr), N.ptr(u_col), N.ptr(ra_edge),
             self.n, N.ptr(lines), N.ptr(ovf), A.n_items, N.ptr(scale.rb), N.ptr(inv_cls), int(j0),
@@ -2291,7 +2316,8 @@ def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop
     in any order, duplicates allowed), for which the interaction, exclusion and eu rows are
     taken as spread_recommend does. ``transpose`` and ``W`` have spread_recommend's meaning.
     tiled=True raises ValueError, as does tiled=None when dense_spread_fits says no: the
-    factored walk prunes by bounds and keeps only bounded lists, so it has no rank."""
+    factored walk prunes by bounds and keeps only bounded lists, so it has no rank -- its ranks
+    come from a walk with a counting finish instead, spread_rank_tiled."""
     dev = A.k_item.device
     if tiled is None:
         tiled = W is None and not dense_spread_fits(A.n_items, dev)
@@ -2343,6 +2369,200 @@ def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop
         rows_rank(Fb, targets.slice_rows(b0, b1),
                   ex.slice_rows(b0, b1) if ex is not None else None, drop,
                   None if eu_r is None else eu_r[b0:b1], ei, out=(rank, val))
+    return rank, val
+
+
+# targets per counting pass of the walk's rank finish (kRankPass, csrc/spread_tiled.hip); rows
+# of any length work, longer ones take ceil(n / SPREAD_RANK_ROW_MAX) passes over the tile in LDS
+SPREAD_RANK_ROW_MAX = N.LG_SPREAD_RANK_ROW_MAX
+
+
+def _entry_rows(rowptr: torch.Tensor, nnz: int):
+    """(row int64 [nnz], inside bool [nnz]) of the entries of a CSR's col: the row that holds
+    position p, and whether any does (a sliced CSR's col has entries outside every row)."""
+    pos = torch.arange(nnz, dtype=torch.int64, device=rowptr.device)
+    row = torch.searchsorted(rowptr, pos, right=True) - 1
+    inside = (pos >= rowptr[0]) & (pos < rowptr[-1])
+    return row.clamp(0, max(rowptr.numel() - 2, 0)), inside
+
+
+def _goto_tile(tw: "TileWeights", j0: int) -> None:
+    """Make [j0, j0 + tile) tw's current tile, from any tile before it: selected when the
+    group built last holds it, built as the next group when it follows the current tile, else
+    built after a seek."""
+    g = tw._grp
+    if g is not None and tw._seek_at is None and g[0] <= j0 < g[0] + sum(g[1]):
+        tw._select((j0 - g[0]) // tw.tile)
+        return
+    if j0 != 0 and (tw.j0 is None or j0 != tw.j0 + tw.width):
+        tw.seek(j0)
+    tw.build(j0)
+
+
+def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None,
+                      drop: bool = True, eu: torch.Tensor | None = None,
+                      ei: torch.Tensor | None = None, users=None, tile: int = 2048,
+                      stats: dict | None = None):
+    """spread_rank on the factored tile walk: where every user's held-out items stand among
+    ALL items under spread_topk_tiled's scores, (G *) A @ HybridS(A, lam), without general_W,
+    W or a row of F ever in memory. (rank int64 [nnz], value fp64 [nnz]) aligned with the
+    target CSR's col, rows_rank's definitions: rank = the ranking columns before the target
+    under (value desc, item asc), 0 = first; -1 for a target that does not rank (its value is
+    NaN or -inf, or drop=True and the user's exclusions name it; its value is still reported);
+    a column named twice gets the same rank twice; an entry of col outside every row and an
+    item id outside the catalog get {-1, -inf}. For every k <= 1024: rank < k iff
+    spread_topk_tiled(A, lam, k, excl, drop, eu, ei, users=..., tile=...) holds the item at
+    [row, rank] with a bit-equal value; the rank itself has no depth limit. Against the dense
+    spread_rank the values agree within 1e-12 relative (the walk's summation order) and the
+    ranks wherever no other value of the row is that close to the target's.
+
+    Two sweeps of lg_spread_tile_resource_rank_f64 over the tiles of TileWeights. Values: the
+    targets are grouped by tile; every tile that holds one is walked by the taken rows of the
+    users with a target there only (bitwise the all-users rows), the kernel writing each
+    target's value -- with one target per user about 1 / ceil(I / tile) of a sweep. Counts:
+    one ascending walk of all rows over all tiles, each adding, per target, the tile's columns
+    before it; with a G factor only columns whose score bound (TileWalk.bounds) reaches the
+    user's worst ranking target value get the exact score. -1 / -inf are filled in on the
+    device. One host read in all (the tiles' group sizes, before the sweeps) besides the tile
+    build's own.
+
+    targets / users as spread_rank: one target row per user, or per entry of ``users`` (ids,
+    any order, duplicates allowed: the user side is taken, the tiles come from the full A).
+    tile: the tile width (<= 4096 with a G factor, 8192 without). No target or no user: no
+    launch. ``stats`` receives the HIP-event times t_build_ms / t_bounds_ms / t_value_ms /
+    t_count_ms and the launches of the two sweeps (value_launches, count_launches)."""
+    dev = A.k_item.device
+    I = A.n_items
+    if eu is not None or ei is not None:
+        _typed(eu, "eu", torch.float32)
+        _typed(ei, "ei", torch.float32)
+        if eu.shape[0] != A.n_users or tuple(ei.shape) != (I, eu.shape[1]):
+            raise ValueError(f"eu must be [{A.n_users}, d] and ei [{I}, d], got "
+                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+        if eu.shape[1] not in (32, 64, 128):
+            raise ValueError(f"embedding width {eu.shape[1]} not in (32, 64, 128)")
+    if excl is not None and excl.n_rows != A.n_users:
+        raise ValueError(f"exclusion rows {excl.n_rows} != users {A.n_users}")
+    if eu is not None and excl is not None and not drop:
+        raise ValueError("a G factor with exclusions requires drop=True")
+    if int(tile) < 1:
+        raise ValueError(f"tile {tile} < 1")
+    ids = None if users is None else _user_ids(users, A.n_users, dev)
+    n = A.n_users if ids is None else int(ids.numel())
+    if isinstance(targets, RowSets) and targets.n_rows != n:
+        raise ValueError(f"target rows {targets.n_rows} != {n} users")
+    targets = candidate_rows(targets, n, I, dev)
+    for t, name in ((targets.col, "targets"), (excl.col if excl is not None else None, "excl"),
+                    (eu, "eu"), (ei, "ei")):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, A on {dev}")
+    nnz = int(targets.col.numel())
+    rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+    val = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
+    if n == 0 or nnz == 0 or I == 0:
+        return rank, val
+    N.require_gpu(A.k_item, "A")
+    L = N.lib()
+    strm = N.stream_handle(dev)
+    tile = min(int(tile), I, 4096 if eu is not None else 8192)  # G: <= 64 chunk bounds
+    ntiles = -(-I // tile)
+    tw = TileWeights(A, lam, tile)
+    by = A.by_user
+    rows = src = None
+    ex = excl if drop else None
+    eu_r = eu
+    if ids is not None:
+        rows, src = by.take(ids, return_index=True)
+        ex = ex.take(ids) if ex is not None else None
+        eu_r = None if eu is None else eu[ids]
+    if ex is not None and ex.col.numel() == 0:
+        ex = None  # (an empty tensor has no pointer to pass)
+    walk = TileWalk(A, 0, n, 0, 1, ex, eu_r, ei, tile, rows=rows, edge_src=src)
+    scale = tw.scale
+    d = walk.d
+
+    # ---- the targets by (tile, row): sorted entries, one group per (tile, row) that has any
+    col = targets.col.to(torch.int64)
+    trow, inside = _entry_rows(targets.rowptr, nnz)
+    valid = inside & (col >= 0) & (col < I)
+    key = torch.where(valid, col // tile, torch.full_like(col, ntiles)) * n + trow
+    skey, perm = torch.sort(key, stable=True)
+    scol = targets.col[perm].contiguous()
+    ukey, gcount = torch.unique_consecutive(skey, return_counts=True)
+    gstart = torch.zeros(ukey.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(gcount, 0, out=gstart[1:])
+    gtile, grow = ukey // n, ukey % n
+    guser = grow if ids is None else ids[grow]
+    gdeg = by.rowptr[guser + 1] - by.rowptr[guser]
+    per_tile = torch.stack([
+        torch.bincount(gtile, minlength=ntiles + 1),
+        torch.bincount(gtile, weights=gdeg.to(torch.float64), minlength=ntiles + 1).to(torch.int64),
+    ]).tolist()  # (the one host read: groups and walked interactions per tile)
+    sval = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
+    evs = {"build": [], "bounds": [], "value": [], "count": []} if stats is not None else None
+
+    def timed(what, fn):
+        if evs is None:
+            return fn()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        out = fn()
+        e[1].record()
+        evs[what].append(e)
+        return out
+
+    # ---- values: the tiles that hold a target, walked by the rows with a target there
+    g0 = 0
+    n_value = 0
+    for t in range(ntiles):
+        ng, total = per_tile[0][t], per_tile[1][t]
+        if ng == 0:
+            continue
+        timed("build", lambda: _goto_tile(tw, t * tile))
+        r = guser[g0:g0 + ng]
+        deg = gdeg[g0:g0 + ng]
+        rp_g = torch.zeros(ng + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(deg, 0, out=rp_g[1:])
+        e_src = torch.repeat_interleave(by.rowptr[r] - rp_g[:-1], deg, output_size=total) \
+            + torch.arange(total, dtype=torch.int64, device=dev)
+        # (one spare entry each: rows without interactions still pass valid pointers)
+        items_g = torch.cat([by.col[e_src], by.col.new_zeros(1)])
+        ra_g = torch.cat([scale.ra_edge[e_src], scale.ra_edge.new_zeros(1)])
+        eu_g = None if eu is None else walk.eu[grow[g0:g0 + ng]].contiguous()
+        tp = gstart[g0:g0 + ng + 1]  # (absolute positions in scol / sval)
+        timed("value", lambda: N.check(L.lg_spread_tile_resource_rank_f64(
+            N.ptr(rp_g), N.ptr(items_g), N.ptr(ra_g), ng, N.ptr(tw.lines), N.ptr(tw.ovf), I,
+            N.ptr(scale.rb), N.ptr(tw.inv_cls), tw.j0, tile, tw.width, N.ptr(eu_g),
+            N.ptr(walk.ei), d, None, 0, None, 0, None, None, None, N.ptr(tp), N.ptr(scol),
+            N.LG_SPREAD_RANK_VALUES, N.ptr(sval), None, total, 0, strm),
+            "lg_spread_tile_resource_rank_f64"))
+        n_value += 1
+        g0 += ng
+    val[perm] = sval
+
+    # ---- counts: every row over every tile, ascending
+    cnt = torch.zeros(nnz, dtype=torch.int64, device=dev)
+    for t in range(ntiles):
+        timed("build", lambda: _goto_tile(tw, t * tile))
+        bnd = timed("bounds", lambda: walk.bounds(tw.j0, tw.width, scale))
+        timed("count", lambda: walk.count_step(tw.lines, tw.ovf, tw.inv_cls, scale, tw.j0, tile,
+                                               tw.width, targets, val, cnt, bnd))
+
+    # ---- a target ranks iff its value is > -inf (not NaN) and no dropped exclusion names it
+    ranks = val > float("-inf")
+    if ex is not None:
+        xrow, xin = _entry_rows(ex.rowptr, int(ex.col.numel()))
+        xkey = torch.where(xin, xrow * I + ex.col.to(torch.int64), torch.full_like(xrow, -1))
+        ranks &= ~torch.isin(trow * I + col, xkey)
+    rank = torch.where(ranks, cnt, rank)
+    if evs is not None:
+        torch.cuda.synchronize(dev)
+        for what, es in evs.items():
+            stats[f"t_{what}_ms"] = stats.get(f"t_{what}_ms", 0.0) + sum(
+                a.elapsed_time(b) for a, b in es)
+        stats["value_launches"] = stats.get("value_launches", 0) + n_value
+        stats["count_launches"] = stats.get("count_launches", 0) + ntiles
+        stats["tiles"] = ntiles
     return rank, val
 
 

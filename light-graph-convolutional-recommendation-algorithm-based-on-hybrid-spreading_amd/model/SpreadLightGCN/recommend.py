@@ -62,14 +62,17 @@ def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.
 
 def spread_lightgcn_ranks(model, user_num: int, item_num: int, train_data_df: pd.DataFrame,
                           val_data_df: pd.DataFrame, held_df: pd.DataFrame, lambda_val: float,
-                          device=None, users=None):
+                          device=None, users=None, tiled: bool | None = None,
+                          tile: int | None = None):
     """(targets RowSets, rank int64 [nnz]): where every held-out (user, item) of ``held_df``
     stands among ALL items for its user under spread_lightgcn_topk's scores G * F -- the same
     interactions, embeddings and dropped train|val items -- so rank < k iff
     spread_lightgcn_topk(..., k) lists the item at that position of the user's row (k <= 1024;
     the rank itself has no depth limit). rank is aligned with targets.col, 0 = first, -1 for an
-    item that does not rank. Dense path only (ops.spread_rank). ``users``: only those users'
-    rows, in that order."""
+    item that does not rank. ``users``: only those users' rows, in that order. ``tiled``: False
+    the dense path (ops.spread_rank), True the factored tile walk (ops.spread_rank_tiled,
+    ``tile`` its tile width), None the dense path when the I x I matrices fit
+    (ops.dense_spread_fits), else the walk -- as spread_lightgcn_topk."""
     from model.SpreadMethod.recommend import held_out_rows
 
     dev = device or gpu_device(model.users_emb.weight)
@@ -80,8 +83,15 @@ def spread_lightgcn_ranks(model, user_num: int, item_num: int, train_data_df: pd
     eu = model.users_emb.weight.detach().to(dev, torch.float32).contiguous()
     ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
     targets = held_out_rows(held_df, user_num, item_num, dev, users)
+    if tiled is None:
+        tiled = not ops.dense_spread_fits(item_num, dev)
+    if tiled:
+        kw = {} if tile is None else {"tile": int(tile)}
+        rank, _ = ops.spread_rank_tiled(inter, lambda_val, targets, inter.by_user, drop=True,
+                                        eu=eu, ei=ei, users=users, **kw)
+        return targets, rank
     rank, _ = ops.spread_rank(inter, lambda_val, targets, inter.by_user, drop=True, eu=eu,
-                              ei=ei, users=users)
+                              ei=ei, users=users, tiled=False)
     return targets, rank
 
 

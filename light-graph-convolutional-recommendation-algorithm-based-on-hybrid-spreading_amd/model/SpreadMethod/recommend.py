@@ -87,14 +87,17 @@ def held_out_rows(held_df: pd.DataFrame, user_num: int, item_num: int, dev, user
 def spread_method_ranks(user_num: int, item_num: int, train_data_df: pd.DataFrame,
                         val_data_df: pd.DataFrame, held_df: pd.DataFrame, method: str,
                         lambda_val: float, dataset: str, unfiltered: bool = False, device=None,
-                        users=None):
+                        users=None, tiled: bool | None = None, tile: int | None = None):
     """(targets RowSets, rank int64 [nnz]): where every held-out (user, item) of ``held_df``
     stands among ALL items for its user under spread_method_topk's scores -- the same
     interactions, per-method overrides, exclusions and drop -- so rank < k iff
     spread_method_topk(..., k) lists the item at that position of the user's row (k <= 1024;
     the rank itself has no depth limit). rank is aligned with targets.col, 0 = first, -1 for an
-    item that does not rank (it is in train|val and those are dropped). Dense path only
-    (ops.spread_rank). ``users``: only those users' rows, in that order."""
+    item that does not rank (it is in train|val and those are dropped). ``users``: only those
+    users' rows, in that order. ``tiled``: False the dense path (ops.spread_rank), True the
+    factored tile walk (ops.spread_rank_tiled, ``tile`` its tile width; general_W is exactly
+    symmetric, so the transpose overrides are served unchanged), None the dense path when the
+    I x I matrices fit (ops.dense_spread_fits), else the walk -- as spread_method_topk."""
     dev = device or gpu_device()
     both = pd.concat([train_data_df, val_data_df])
     inter = ops.Interactions.from_pairs(
@@ -106,8 +109,15 @@ def spread_method_ranks(user_num: int, item_num: int, train_data_df: pd.DataFram
     elif method == "HeatS" and dataset == "douban":  # reference :97-101
         lambda_val, transpose = 0.99, True
     targets = held_out_rows(held_df, user_num, item_num, dev, users)
+    if tiled is None:
+        tiled = not ops.dense_spread_fits(item_num, dev)
+    if tiled:
+        kw = {} if tile is None else {"tile": int(tile)}
+        rank, _ = ops.spread_rank_tiled(inter, lambda_val, targets, inter.by_user,
+                                        drop=not unfiltered, users=users, **kw)
+        return targets, rank
     rank, _ = ops.spread_rank(inter, lambda_val, targets, inter.by_user, drop=not unfiltered,
-                              transpose=transpose, users=users)
+                              transpose=transpose, users=users, tiled=False)
     return targets, rank
 
 
