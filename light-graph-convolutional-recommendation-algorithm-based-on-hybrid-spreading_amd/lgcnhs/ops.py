@@ -78,6 +78,54 @@ def _same_device(t: torch.Tensor, name: str, ref: torch.Tensor, ref_name: str) -
         raise ValueError(f"{name} is on {t.device}, {ref_name} on {ref.device}")
 
 
+def _nonempty(rowsets):
+    """rowsets, or None when it holds no entry at all (an empty tensor has no pointer to pass)."""
+    return None if rowsets is None or rowsets.col.numel() == 0 else rowsets
+
+
+def _g_guard(eu, ei, n: int, m: int, what: str = "") -> None:
+    """The G factor's operands: TypeError unless eu and ei are both float32 matrices (a half-set
+    pair fails here), ValueError unless they are [n, d] and [m, d]; ``what`` opens the message."""
+    _typed(eu, "eu", torch.float32)
+    _typed(ei, "ei", torch.float32)
+    if eu.shape[0] != n or ei.shape[0] != m or eu.shape[1] != ei.shape[1]:
+        raise ValueError(f"{what}eu must be [{n}, d] and ei [{m}, d], got "
+                         f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+
+
+def _excl_guard(excl, n: int, what: str, g_keeps: bool = False) -> None:
+    """ValueError unless excl (or None) has n rows, ``what`` naming them; g_keeps: the call has
+    a G factor and drop=False, which no kernel serves together with exclusions."""
+    if excl is None:
+        return
+    if excl.n_rows != n:
+        raise ValueError(f"exclusion rows {excl.n_rows} != {what} {n}")
+    if g_keeps:
+        raise ValueError("a G factor with exclusions requires drop=True")
+
+
+def _mark(evs, what) -> None:
+    """stats= timing: one HIP event on the launch stream that ends the open stage and starts
+    stage ``what`` (None: ends only). evs None (no stats= asked for): nothing, no event."""
+    if evs is not None:
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        evs.append((what, e))
+
+
+def _stage_ms(stats: dict, evs: list, dev, *stages) -> dict:
+    """One synchronize, then stats["t_<stage>_ms"] grows by the marked spans of each stage;
+    returns {stage: [ms per span]}."""
+    torch.cuda.synchronize(dev)
+    ms = {w: [] for w in stages}
+    for (w, a), (_, b) in zip(evs, evs[1:]):
+        if w is not None:
+            ms[w].append(a.elapsed_time(b))
+    for w, t in ms.items():
+        stats[f"t_{w}_ms"] = stats.get(f"t_{w}_ms", 0.0) + sum(t)
+    return ms
+
+
 def _layer_operand(t, name: str, x: torch.Tensor, dtype) -> None:
     """y / x0 / acc / out of run_layer: None, or x's shape and device, contiguous, of `dtype`."""
     if t is None:
@@ -775,9 +823,7 @@ def _score_topk_gathered(eu, ei, cand, k, excl, mask_value, **kw):
     """score_topk on the sub-table ei[cand] (exclusion columns renumbered to positions in
     cand), ids mapped back through cand, -1 kept."""
     c64 = cand.to(torch.int64)
-    ex = excl.restrict_cols(cand) if excl is not None else None
-    if ex is not None and ex.col.numel() == 0:
-        ex = None  # (no excluded candidate at all: an empty tensor has no pointer to pass)
+    ex = _nonempty(excl.restrict_cols(cand) if excl is not None else None)
     v, i = score_topk(eu, ei[c64], k, ex, mask_value, **kw)
     return v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
 
@@ -841,10 +887,8 @@ def score_topk_users(eu: torch.Tensor, ei: torch.Tensor, users, k: int,
                                         mask_value)
         if k < 1:
             raise ValueError(f"k={k} not in [1, {WIDE_K_MAX}]")
-        if excl is not None and excl.col.numel() == 0:
-            excl = None  # (an empty tensor has no pointer to pass)
-        return _topk_lists("lg_score_topk_batch_items", ITEMS_CALL_USERS, eu, ei, ids, k, excl,
-                           mask_value, cand)
+        return _topk_lists("lg_score_topk_batch_items", ITEMS_CALL_USERS, eu, ei, ids, k,
+                           _nonempty(excl), mask_value, cand)
     if nb == 0 or nb > BATCH_MAX_USERS or k > BATCH_K_MAX:
         return score_topk(eu[ids], ei, k, excl.take(ids) if excl is not None else None,
                           mask_value)
@@ -949,8 +993,7 @@ def _cand_args(eu, ei, cand, excl, users, max_len):
         raise ValueError(f"candidate columns {cand.n_cols} != items {ei.shape[0]}")
     if excl is not None and excl.n_rows != nu:
         raise ValueError(f"exclusion rows {excl.n_rows} != users {nu}")
-    if excl is not None and excl.col.numel() == 0:
-        excl = None  # (an empty tensor has no pointer to pass)
+    excl = _nonempty(excl)
     ids = None
     if users is not None:
         ids = _user_ids(users, nu, eu.device)
@@ -1213,9 +1256,7 @@ def spread_resource(A: Interactions, W: torch.Tensor, users: slice | None = None
     columns [0, I) are written; its row stride is kept)."""
     u0, u1 = (0, A.n_users) if users is None else (users.start, users.stop)
     I = A.n_items
-    _typed(W, "W", torch.float64)
-    if tuple(W.shape) != (I, I):
-        raise ValueError(f"W has shape {tuple(W.shape)}, expected ({I}, {I})")
+    _check_W(W, I)
     _same_device(W, "W", A.by_user.col, "A")
     if not 0 <= u0 <= u1 <= A.n_users:
         raise ValueError(f"users [{u0}, {u1}) outside [0, {A.n_users}]")
@@ -1228,10 +1269,43 @@ def spread_resource(A: Interactions, W: torch.Tensor, users: slice | None = None
     W = _f64(W, "W")
     F = out if out is not None else torch.empty((u1 - u0, I), dtype=torch.float64,
                                                 device=W.device)
-    N.check(N.lib().lg_spread_resource_f64(
-        N.ptr(A.by_user.rowptr[u0:]), N.ptr(A.by_user.col), N.ptr(W), u1 - u0, A.n_items,
-        N.ptr(F), F.stride(0), N.stream_handle(W.device)), "lg_spread_resource_f64")
+    _resource_rows(A.by_user.rowptr[u0:], A.by_user.col, W, u1 - u0, F)
     return F
+
+
+F_BLOCK_BYTES = 1 << 30  # of F per block of _f_blocks (read at call time)
+
+
+def _check_W(W, I: int, expected: str | None = None) -> None:
+    """TypeError / ValueError unless W is a float64 [I, I] tensor (no device check): the one
+    check of the W that _f_blocks and spread_resource read."""
+    _typed(W, "W", torch.float64)
+    if tuple(W.shape) != (I, I):
+        raise ValueError(f"W has shape {tuple(W.shape)}, expected {expected or f'({I}, {I})'}")
+
+
+def _resource_rows(rowptr, col, W, n: int, F) -> None:
+    """F[:n] = the n rows that start at rowptr (offsets into col) times the checked W."""
+    N.check(N.lib().lg_spread_resource_f64(
+        N.ptr(rowptr), N.ptr(col), N.ptr(W), n, W.shape[0], N.ptr(F), F.stride(0),
+        N.stream_handle(W.device)), "lg_spread_resource_f64")
+
+
+def _f_blocks(rows: RowSets, W: torch.Tensor, block_users: int | None = None):
+    """Yield (b0, b1, Fb) over row blocks of F = rows @ W (rows: A.by_user or taken rows of
+    it): Fb = F[b0:b1] in one reused float64 buffer, overwritten by the next block.
+    F_BLOCK_BYTES of F per block, or block_users rows. W: checked by the caller (_check_W)."""
+    n, I = rows.n_rows, rows.n_cols
+    _same_device(W, "W", rows.col, "A")
+    N.require_gpu(W, "W")
+    W = _aligned(W)
+    block = max(1, min(n, F_BLOCK_BYTES // max(1, I * 8))) if block_users is None \
+        else max(1, int(block_users))
+    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=W.device)
+    for b0 in range(0, n, block):
+        b1 = min(n, b0 + block)
+        _resource_rows(rows.rowptr[b0:], rows.col, W, b1 - b0, buf)
+        yield b0, b1, buf[: b1 - b0]
 
 
 def rows_topk(F: torch.Tensor, k: int, excl: RowSets | None = None, drop: bool = True,
@@ -1246,13 +1320,8 @@ def rows_topk(F: torch.Tensor, k: int, excl: RowSets | None = None, drop: bool =
     _typed(F, "F", torch.float64)
     n, m = F.shape
     if eu is not None:
-        _typed(eu, "eu", torch.float32)
-        _typed(ei, "ei", torch.float32)
-        if eu.shape[0] != n or ei.shape[0] != m or eu.shape[1] != ei.shape[1]:
-            raise ValueError(f"F is {n} x {m}: eu must be [{n}, d] and ei [{m}, d], got "
-                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
-    if excl is not None and excl.n_rows != n:
-        raise ValueError(f"exclusion rows {excl.n_rows} != rows of F {n}")
+        _g_guard(eu, ei, n, m, f"F is {n} x {m}: ")
+    _excl_guard(excl, n, "rows of F")
     N.require_gpu(F, "F")
     if F.numel() and (F.stride(1) != 1 or F.data_ptr() % 16):
         F = _aligned(F)  # (a row-strided view of a larger buffer is taken as it is)
@@ -1276,18 +1345,20 @@ def spread_topk(A: Interactions, W: torch.Tensor, k: int, excl: RowSets | None,
                 ei: torch.Tensor | None = None, block_users: int | None = None):
     """F = A @ W computed block by block and reduced to per-user top-k without ever
     holding all of F (the fused recommend path of SpreadMethod / SpreadLightGCN)."""
-    U, I = A.n_users, A.n_items
-    if block_users is None:
-        block_users = max(1, min(U, (1 << 30) // max(1, I * 8)))  # ~1 GiB of F per block
-    vals = torch.empty((U, k), dtype=torch.float64, device=W.device)
-    idxs = torch.empty((U, k), dtype=torch.int64, device=W.device)
-    buf = torch.empty((min(block_users, U), I), dtype=torch.float64, device=W.device)
-    for u0 in range(0, U, block_users):
-        u1 = min(U, u0 + block_users)
-        Fb = spread_resource(A, W, slice(u0, u1), out=buf[: u1 - u0])
-        ex = excl.slice_rows(u0, u1) if excl is not None else None
-        v, i = rows_topk(Fb, k, ex, drop, None if eu is None else eu[u0:u1], ei)
-        vals[u0:u1], idxs[u0:u1] = v, i
+    return _blocks_topk(A.by_user, W, k, excl, drop, eu, ei, block_users)
+
+
+def _blocks_topk(rows: RowSets, W: torch.Tensor, k: int, ex: RowSets | None, drop: bool,
+                 eu_r, ei, block_users: int | None = None):
+    """rows_topk of every F block of ``rows`` (ex, eu_r: their exclusion and eu rows)."""
+    n = rows.n_rows
+    _check_W(W, rows.n_cols)
+    vals = torch.empty((n, k), dtype=torch.float64, device=W.device)
+    idxs = torch.empty((n, k), dtype=torch.int64, device=W.device)
+    for b0, b1, Fb in _f_blocks(rows, W, block_users):
+        vals[b0:b1], idxs[b0:b1] = rows_topk(
+            Fb, k, ex.slice_rows(b0, b1) if ex is not None else None, drop,
+            None if eu_r is None else eu_r[b0:b1], ei)
     return vals, idxs
 
 
@@ -1315,15 +1386,8 @@ def rows_rank(F: torch.Tensor, targets, excl: RowSets | None = None, drop: bool 
     _typed(F, "F", torch.float64)
     n, m = F.shape
     if eu is not None or ei is not None:
-        _typed(eu, "eu", torch.float32)
-        _typed(ei, "ei", torch.float32)
-        if eu.shape[0] != n or ei.shape[0] != m or eu.shape[1] != ei.shape[1]:
-            raise ValueError(f"F is {n} x {m}: eu must be [{n}, d] and ei [{m}, d], got "
-                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
-    if excl is not None and excl.n_rows != n:
-        raise ValueError(f"exclusion rows {excl.n_rows} != rows of F {n}")
-    if eu is not None and excl is not None and not drop:
-        raise ValueError("a G factor with exclusions requires drop=True")
+        _g_guard(eu, ei, n, m, f"F is {n} x {m}: ")
+    _excl_guard(excl, n, "rows of F", eu is not None and not drop)
     if isinstance(targets, RowSets) and targets.n_rows != n:
         raise ValueError(f"target rows {targets.n_rows} != rows of F {n}")
     N.require_gpu(F, "F")
@@ -1339,8 +1403,7 @@ def rows_rank(F: torch.Tensor, targets, excl: RowSets | None = None, drop: bool 
     if eu is not None:
         eu, ei = _f32_tables(eu, ei)
         d = eu.shape[1]
-    if excl is not None and excl.col.numel() == 0:
-        excl = None  # (an empty tensor has no pointer to pass)
+    excl = _nonempty(excl)
     nnz = int(targets.col.numel())
     if out is None:
         rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
@@ -1698,6 +1761,26 @@ class TileWeights:
                                torch.full_like(used, 1 + (self.width + 1) // 2), used)
             self.bytes_read += 128 * self.row_uses.sum() + 16 * (self.row_uses * used).sum()
 
+
+def _walk_tile(tile: int, n_cols: int, g: bool) -> int:
+    """The walk's tile width: no wider than its columns, than 4096 with a G factor (64 chunk
+    bounds of 64 columns) and than 8192 without."""
+    return min(int(tile), n_cols, 4096 if g else 8192)
+
+
+def _user_side(A: Interactions, ids, excl: RowSets | None, eu, return_index: bool = False):
+    """(rows, edge_src, ex, eu_r): the interaction, exclusion and eu rows of the users ``ids``
+    (RowSets.take, eu[ids]; edge_src: with return_index the taken entries' positions in
+    A.by_user.col, else None). ids None: A.by_user, None, excl and eu themselves -- no copy, no
+    host read."""
+    if ids is None:
+        return A.by_user, None, excl, eu
+    rows, src = A.by_user.take(ids, return_index=True) if return_index \
+        else (A.by_user.take(ids), None)
+    return (rows, src, None if excl is None else excl.take(ids),
+            None if eu is None else eu[ids])
+
+
 def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
                       drop: bool = True, eu: torch.Tensor | None = None,
                       ei: torch.Tensor | None = None, users=None,
@@ -1771,7 +1854,7 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
     if n == 0 or i1 <= i0:
         return vals, idxs
-    tile = min(int(tile), i1 - i0, 4096 if eu is not None else 8192)  # G: <= 64 chunk bounds
+    tile = _walk_tile(tile, i1 - i0, eu is not None)
     tw = TileWeights(A, lam, tile, cols=cand)
     if i0:
         tw.seek(i0)
@@ -1780,9 +1863,7 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
         # the user side from the taken rows; the item side (the tiles) from the full A
         if stats is not None and count_paths:
             raise ValueError("count_paths takes a user range, not user ids")
-        rows, src = A.by_user.take(ids, return_index=True)
-        ex = excl.take(ids) if excl is not None else None
-        eu_r = None if eu is None else eu[ids]
+        rows, src, ex, eu_r = _user_side(A, ids, excl, eu, return_index=True)
     else:
         ex = excl.slice_rows(u0, u1) if excl is not None else None
         eu_r = None if eu is None else eu[u0:u1]
@@ -1790,31 +1871,22 @@ def spread_topk_tiled(A: Interactions, lam: float, k: int, excl: RowSets | None,
         _count_rows(tw, A, u0, u1)
     walk = TileWalk(A, u0, u1, i0, k, ex if drop else None, eu_r, ei, tile, col_bounds,
                     rows=rows, edge_src=src, cols=cand)
-    evs = [] if stats is not None else None
+    evs = [] if stats is not None else None  # (per tile: build / bounds / walk, back to back)
     for j0 in range(i0, i1, tile):
-        if evs is not None:  # per-tile HIP events on the launch stream: build / bounds / walk
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            e[0].record()
+        _mark(evs, "build")
         tw.build(j0, stop=i1)
-        if evs is not None:
-            e[1].record()
+        _mark(evs, "bounds")
         bnd = walk.bounds(j0, tw.width, tw.scale)
-        if evs is not None:
-            e[2].record()
+        _mark(evs, "walk")
         walk.step(tw.lines, tw.ovf, tw.inv_cls, tw.scale, j0, tile, tw.width, j0 == i0, bnd)
-        if evs is not None:
-            e[3].record()
-            evs.append(e)
+    _mark(evs, None)
     vals.copy_(walk.vals)
     idxs.copy_(walk.item_ids())
-    if evs:
-        torch.cuda.synchronize(dev)
-        stats["t_build_ms"] = stats.get("t_build_ms", 0.0) + sum(e[0].elapsed_time(e[1]) for e in evs)
-        stats["t_bounds_ms"] = stats.get("t_bounds_ms", 0.0) + sum(e[1].elapsed_time(e[2]) for e in evs)
-        stats["t_walk_ms"] = stats.get("t_walk_ms", 0.0) + sum(e[2].elapsed_time(e[3]) for e in evs)
-        stats["walk_launches"] = stats.get("walk_launches", 0) + len(evs)
-        stats["walk_ms_list"] = stats.get("walk_ms_list", []) + [e[2].elapsed_time(e[3]) for e in evs]
-        stats["user_items"] = stats.get("user_items", 0) + len(evs) * int(
+    if evs is not None:
+        ms = _stage_ms(stats, evs, dev, "build", "bounds", "walk")["walk"]
+        stats["walk_launches"] = stats.get("walk_launches", 0) + len(ms)
+        stats["walk_ms_list"] = stats.get("walk_ms_list", []) + ms
+        stats["user_items"] = stats.get("user_items", 0) + len(ms) * int(
             rows.col.numel() if rows is not None
             else A.by_user.rowptr[u1] - A.by_user.rowptr[u0])
         stats["users"] = n
@@ -1851,7 +1923,7 @@ def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
     ex = excl if drop else None
     n_rows = excl.n_rows if excl is not None else A.n_users
-    evs = []
+    evs = [] if stats is not None else None
     for c0 in range(0, k, PEEL_K):
         kp = min(PEEL_K, k - c0)
         v, i = spread_topk_tiled(A, lam, kp, ex, True, eu, ei, users=users, tile=tile,
@@ -1860,19 +1932,14 @@ def _spread_topk_tiled_peeled(A: Interactions, lam: float, k: int, excl: RowSets
         vals[:, c0:c0 + kp], idxs[:, c0:c0 + kp] = v, i
         if c0 + kp >= k or not bool((i[:, kp - 1] >= 0).any()):
             break  # (a row whose last entry is empty has no survivors left)
-        if stats is not None:
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            e[0].record()
+        _mark(evs, "excl")
         hit = (i >= 0).nonzero(as_tuple=True)
         found = RowSets.from_pairs(hit[0] + u0 if ids is None else ids[hit[0]], i[hit], n_rows,
                                    A.n_items, dev)
         ex = found if ex is None else RowSets.union(ex, found)
-        if stats is not None:
-            e[1].record()
-            evs.append(e)
-    if stats is not None:
-        torch.cuda.synchronize(dev)
-        stats["t_excl_ms"] = stats.get("t_excl_ms", 0.0) + sum(a.elapsed_time(b) for a, b in evs)
+        _mark(evs, None)
+    if evs is not None:
+        _stage_ms(stats, evs, dev, "excl")
         stats["peel_passes"] = stats.get("peel_passes", 0) + c0 // PEEL_K + 1
     return vals, idxs
 
@@ -1990,9 +2057,7 @@ class TileWalk:
                  cols: torch.Tensor | None = None):
         self.cols = cols
         if cols is not None:
-            ex = ex.restrict_cols(cols) if ex is not None else None
-            if ex is not None and ex.col.numel() == 0:
-                ex = None  # (no excluded candidate at all: an empty tensor has no pointer)
+            ex = _nonempty(ex.restrict_cols(cols) if ex is not None else None)
             ei = ei[cols.to(torch.int64)] if ei is not None else None
         self.A, self.u0, self.u1, self.i0, self.k, self.ex = A, u0, u1, i0, int(k), ex
         # the walk keeps its stream positions in 32 bits
@@ -2152,7 +2217,7 @@ def spread_lambda_sweep(A: Interactions, lams, k: int, excl: RowSets | None,
     if cache_bytes is None:
         cache_bytes = torch.cuda.mem_get_info(dev)[0] // 2
     U, I = A.n_users, A.n_items
-    tile = min(int(tile), I, 4096 if eu is not None else 8192) if I else 1
+    tile = _walk_tile(tile, I, eu is not None) if I else 1
     ex = excl if drop else None
     walk = TileWalk(A, 0, U, 0, k, ex, eu, ei, tile)
     cache, used, cached = [], 0, True
@@ -2275,29 +2340,10 @@ def spread_recommend(A: Interactions, lam: float, k: int, excl: RowSets | None,
 
 def _spread_topk_users(A: Interactions, W: torch.Tensor, ids: torch.Tensor, k: int,
                        excl: RowSets | None, drop: bool, eu, ei):
-    """spread_topk for the users ``ids`` only: lg_spread_resource_f64 on the taken
-    interaction rows (F rows of those users, block by block), then rows_topk with the taken
-    exclusion and eu rows."""
-    I = A.n_items
-    rows = A.by_user.take(ids)
-    ex = excl.take(ids) if excl is not None else None
-    eu_r = None if eu is None else eu[ids]
-    n = rows.n_rows
-    W = W.contiguous()
-    vals = torch.empty((n, k), dtype=torch.float64, device=W.device)
-    idxs = torch.empty((n, k), dtype=torch.int64, device=W.device)
-    block = max(1, min(n, (1 << 30) // max(1, I * 8)))  # ~1 GiB of F per block
-    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=W.device)
-    for b0 in range(0, n, block):
-        b1 = min(n, b0 + block)
-        Fb = buf[: b1 - b0]
-        N.check(N.lib().lg_spread_resource_f64(
-            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
-            Fb.stride(0), N.stream_handle(W.device)), "lg_spread_resource_f64")
-        v, i = rows_topk(Fb, k, ex.slice_rows(b0, b1) if ex is not None else None, drop,
-                         None if eu_r is None else eu_r[b0:b1], ei)
-        vals[b0:b1], idxs[b0:b1] = v, i
-    return vals, idxs
+    """spread_topk for the users ``ids`` only: the F rows of the taken interaction rows, block
+    by block, then rows_topk with the taken exclusion and eu rows."""
+    rows, _, ex, eu_r = _user_side(A, ids, excl, eu)
+    return _blocks_topk(rows, W, k, ex, drop, eu_r, ei)
 
 
 def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop: bool = True,
@@ -2327,18 +2373,10 @@ def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop
                          "dense path (the I x I matrices on the device, tiled=False or W=)")
     I = A.n_items
     if W is not None:
-        _typed(W, "W", torch.float64)
-        if tuple(W.shape) != (I, I):
-            raise ValueError(f"W has shape {tuple(W.shape)}, expected the fp64 ({I}, {I}) "
-                             f"matrix of spread_hybrid")
+        _check_W(W, I, f"the fp64 ({I}, {I}) matrix of spread_hybrid")
     if eu is not None or ei is not None:
-        _typed(eu, "eu", torch.float32)
-        _typed(ei, "ei", torch.float32)
-        if eu.shape[0] != A.n_users or tuple(ei.shape) != (I, eu.shape[1]):
-            raise ValueError(f"eu must be [{A.n_users}, d] and ei [{I}, d], got "
-                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
-    if excl is not None and excl.n_rows != A.n_users:
-        raise ValueError(f"exclusion rows {excl.n_rows} != users {A.n_users}")
+        _g_guard(eu, ei, A.n_users, I)
+    _excl_guard(excl, A.n_users, "users")
     ids = None if users is None else _user_ids(users, A.n_users, dev)
     n = A.n_users if ids is None else int(ids.numel())
     if isinstance(targets, RowSets) and targets.n_rows != n:
@@ -2351,19 +2389,8 @@ def spread_rank(A: Interactions, lam: float, targets, excl: RowSets | None, drop
         return rank, val
     if W is None:
         W = spread_hybrid(A, lam)
-    W = _f64(W, "W")
-    rows = A.by_user if ids is None else A.by_user.take(ids)
-    ex = excl if ids is None or excl is None else excl.take(ids)
-    eu_r = eu if ids is None or eu is None else eu[ids]
-    block = max(1, min(n, (1 << 30) // max(1, I * 8))) if block_users is None \
-        else max(1, int(block_users))  # ~1 GiB of F per block
-    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=dev)
-    for b0 in range(0, n, block):
-        b1 = min(n, b0 + block)
-        Fb = buf[: b1 - b0]
-        N.check(N.lib().lg_spread_resource_f64(
-            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
-            Fb.stride(0), N.stream_handle(dev)), "lg_spread_resource_f64")
+    rows, _, ex, eu_r = _user_side(A, ids, excl, eu)
+    for b0, b1, Fb in _f_blocks(rows, W, block_users):
         # the block's targets keep their absolute offsets into col: every block writes its own
         # entries of the [nnz] outputs
         rows_rank(Fb, targets.slice_rows(b0, b1),
@@ -2434,17 +2461,10 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
     dev = A.k_item.device
     I = A.n_items
     if eu is not None or ei is not None:
-        _typed(eu, "eu", torch.float32)
-        _typed(ei, "ei", torch.float32)
-        if eu.shape[0] != A.n_users or tuple(ei.shape) != (I, eu.shape[1]):
-            raise ValueError(f"eu must be [{A.n_users}, d] and ei [{I}, d], got "
-                             f"{tuple(eu.shape)} and {tuple(ei.shape)}")
+        _g_guard(eu, ei, A.n_users, I)
         if eu.shape[1] not in (32, 64, 128):
             raise ValueError(f"embedding width {eu.shape[1]} not in (32, 64, 128)")
-    if excl is not None and excl.n_rows != A.n_users:
-        raise ValueError(f"exclusion rows {excl.n_rows} != users {A.n_users}")
-    if eu is not None and excl is not None and not drop:
-        raise ValueError("a G factor with exclusions requires drop=True")
+    _excl_guard(excl, A.n_users, "users", eu is not None and not drop)
     if int(tile) < 1:
         raise ValueError(f"tile {tile} < 1")
     ids = None if users is None else _user_ids(users, A.n_users, dev)
@@ -2464,19 +2484,14 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
     N.require_gpu(A.k_item, "A")
     L = N.lib()
     strm = N.stream_handle(dev)
-    tile = min(int(tile), I, 4096 if eu is not None else 8192)  # G: <= 64 chunk bounds
+    tile = _walk_tile(tile, I, eu is not None)
     ntiles = -(-I // tile)
     tw = TileWeights(A, lam, tile)
     by = A.by_user
-    rows = src = None
-    ex = excl if drop else None
-    eu_r = eu
+    rows, src, ex, eu_r = None, None, excl if drop else None, eu
     if ids is not None:
-        rows, src = by.take(ids, return_index=True)
-        ex = ex.take(ids) if ex is not None else None
-        eu_r = None if eu is None else eu[ids]
-    if ex is not None and ex.col.numel() == 0:
-        ex = None  # (an empty tensor has no pointer to pass)
+        rows, src, ex, eu_r = _user_side(A, ids, ex, eu, return_index=True)
+    ex = _nonempty(ex)
     walk = TileWalk(A, 0, n, 0, 1, ex, eu_r, ei, tile, rows=rows, edge_src=src)
     scale = tw.scale
     d = walk.d
@@ -2499,17 +2514,7 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
         torch.bincount(gtile, weights=gdeg.to(torch.float64), minlength=ntiles + 1).to(torch.int64),
     ]).tolist()  # (the one host read: groups and walked interactions per tile)
     sval = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
-    evs = {"build": [], "bounds": [], "value": [], "count": []} if stats is not None else None
-
-    def timed(what, fn):
-        if evs is None:
-            return fn()
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        e[0].record()
-        out = fn()
-        e[1].record()
-        evs[what].append(e)
-        return out
+    evs = [] if stats is not None else None
 
     # ---- values: the tiles that hold a target, walked by the rows with a target there
     g0 = 0
@@ -2518,7 +2523,9 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
         ng, total = per_tile[0][t], per_tile[1][t]
         if ng == 0:
             continue
-        timed("build", lambda: _goto_tile(tw, t * tile))
+        _mark(evs, "build")
+        _goto_tile(tw, t * tile)
+        _mark(evs, None)
         r = guser[g0:g0 + ng]
         deg = gdeg[g0:g0 + ng]
         rp_g = torch.zeros(ng + 1, dtype=torch.int64, device=dev)
@@ -2530,12 +2537,14 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
         ra_g = torch.cat([scale.ra_edge[e_src], scale.ra_edge.new_zeros(1)])
         eu_g = None if eu is None else walk.eu[grow[g0:g0 + ng]].contiguous()
         tp = gstart[g0:g0 + ng + 1]  # (absolute positions in scol / sval)
-        timed("value", lambda: N.check(L.lg_spread_tile_resource_rank_f64(
+        _mark(evs, "value")
+        N.check(L.lg_spread_tile_resource_rank_f64(
             N.ptr(rp_g), N.ptr(items_g), N.ptr(ra_g), ng, N.ptr(tw.lines), N.ptr(tw.ovf), I,
             N.ptr(scale.rb), N.ptr(tw.inv_cls), tw.j0, tile, tw.width, N.ptr(eu_g),
             N.ptr(walk.ei), d, None, 0, None, 0, None, None, None, N.ptr(tp), N.ptr(scol),
             N.LG_SPREAD_RANK_VALUES, N.ptr(sval), None, total, 0, strm),
-            "lg_spread_tile_resource_rank_f64"))
+            "lg_spread_tile_resource_rank_f64")
+        _mark(evs, None)
         n_value += 1
         g0 += ng
     val[perm] = sval
@@ -2543,10 +2552,14 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
     # ---- counts: every row over every tile, ascending
     cnt = torch.zeros(nnz, dtype=torch.int64, device=dev)
     for t in range(ntiles):
-        timed("build", lambda: _goto_tile(tw, t * tile))
-        bnd = timed("bounds", lambda: walk.bounds(tw.j0, tw.width, scale))
-        timed("count", lambda: walk.count_step(tw.lines, tw.ovf, tw.inv_cls, scale, tw.j0, tile,
-                                               tw.width, targets, val, cnt, bnd))
+        _mark(evs, "build")
+        _goto_tile(tw, t * tile)
+        _mark(evs, "bounds")
+        bnd = walk.bounds(tw.j0, tw.width, scale)
+        _mark(evs, "count")
+        walk.count_step(tw.lines, tw.ovf, tw.inv_cls, scale, tw.j0, tile, tw.width, targets, val,
+                        cnt, bnd)
+    _mark(evs, None)
 
     # ---- a target ranks iff its value is > -inf (not NaN) and no dropped exclusion names it
     ranks = val > float("-inf")
@@ -2556,10 +2569,7 @@ def spread_rank_tiled(A: Interactions, lam: float, targets, excl: RowSets | None
         ranks &= ~torch.isin(trow * I + col, xkey)
     rank = torch.where(ranks, cnt, rank)
     if evs is not None:
-        torch.cuda.synchronize(dev)
-        for what, es in evs.items():
-            stats[f"t_{what}_ms"] = stats.get(f"t_{what}_ms", 0.0) + sum(
-                a.elapsed_time(b) for a, b in es)
+        _stage_ms(stats, evs, dev, "build", "bounds", "value", "count")
         stats["value_launches"] = stats.get("value_launches", 0) + n_value
         stats["count_launches"] = stats.get("count_launches", 0) + ntiles
         stats["tiles"] = ntiles
@@ -2599,10 +2609,8 @@ def spread_rows_topk_items(rows: RowSets, W: torch.Tensor, cand: torch.Tensor, k
     # that is never read -- the entry pads every row on n_cand = 0, rows without items sum to 0)
     cand_p = cand if nc else torch.zeros(1, dtype=torch.int32, device=dev)
     col_p = rows.col if rows.col.numel() else torch.zeros(1, dtype=torch.int32, device=dev)
-    if excl is not None and excl.n_rows != n:
-        raise ValueError(f"exclusion rows {excl.n_rows} != rows {n}")
-    if excl is not None and excl.col.numel() == 0:
-        excl = None  # (an empty tensor has no pointer to pass)
+    _excl_guard(excl, n, "rows")
+    excl = _nonempty(excl)
     d = 0
     if eu is not None:
         eu, ei = _f32_tables(eu, ei)
@@ -2620,7 +2628,7 @@ def spread_rows_topk_items(rows: RowSets, W: torch.Tensor, cand: torch.Tensor, k
 
 
 # spread_recommend(items=...) on the dense path sends a request to the fused kernel
-# (lg_spread_rows_topk_items_f64) or to the existing pair -- lg_spread_resource_f64, an F[:, C]
+# (lg_spread_rows_topk_items_f64) or to the existing pair -- the F blocks, an F[:, C]
 # gather, rows_topk, the id map -- whichever profiles/spread_items.json
 # (scripts/spread_items_time.py: 600 x 20,000, d = 64, with and without G, users 1 / 8 / 16 /
 # 600, share 1.0 / 0.5 / 0.1 / 0.01, k 20 / 100 / 256) measured faster by more than the larger
@@ -2648,22 +2656,19 @@ def _spread_topk_items(A: Interactions, W: torch.Tensor, ids, cand: torch.Tensor
                        excl: RowSets | None, drop: bool, eu, ei, route: str | None = None):
     """spread_recommend's dense path over the candidates ``cand`` for all users (ids None)
     or the users ``ids`` (interaction, exclusion and eu rows taken as _spread_topk_users
-    does). route: "fused" (lg_spread_rows_topk_items_f64), "gather" (lg_spread_resource_f64
-    block by block, F[:, cand], rows_topk on the renumbered exclusions and ei[cand], ids
-    mapped back) or None: _spread_items_route. Bitwise the same lists either way."""
-    I = A.n_items
-    rows = A.by_user if ids is None else A.by_user.take(ids)
-    ex = excl if ids is None or excl is None else excl.take(ids)
-    eu_r = eu if ids is None or eu is None else eu[ids]
+    does). route: "fused" (lg_spread_rows_topk_items_f64), "gather" (F block by block,
+    F[:, cand], rows_topk on the renumbered exclusions and ei[cand], ids mapped back) or
+    None: _spread_items_route. Bitwise the same lists either way."""
+    rows, _, ex, eu_r = _user_side(A, ids, excl, eu)
     n, nc = rows.n_rows, int(cand.numel())
     if route is None:
-        route = _spread_items_route(n, nc, I)
+        route = _spread_items_route(n, nc, A.n_items)
     if route == "fused":
         return spread_rows_topk_items(rows, W, cand, k, ex, drop, eu_r, ei)
     if route != "gather":
         raise ValueError(f"route {route!r} not in ('fused', 'gather')")
     k = int(k)
-    W = W.contiguous()
+    _check_W(W, A.n_items)
     dev = W.device
     vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
     idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
@@ -2672,18 +2677,9 @@ def _spread_topk_items(A: Interactions, W: torch.Tensor, ids, cand: torch.Tensor
             raise ValueError(f"k={k} not in [1, 1024]")
         return vals, idxs
     c64 = cand.to(torch.int64)
-    exc = ex.restrict_cols(cand) if ex is not None else None
-    if exc is not None and exc.col.numel() == 0:
-        exc = None  # (no excluded candidate at all: an empty tensor has no pointer to pass)
+    exc = _nonempty(ex.restrict_cols(cand) if ex is not None else None)
     eic = None if ei is None else ei[c64]
-    block = max(1, min(n, (1 << 30) // max(1, I * 8)))  # ~1 GiB of F per block
-    buf = torch.empty((min(block, n), I), dtype=torch.float64, device=dev)
-    for b0 in range(0, n, block):
-        b1 = min(n, b0 + block)
-        Fb = buf[: b1 - b0]
-        N.check(N.lib().lg_spread_resource_f64(
-            N.ptr(rows.rowptr[b0:]), N.ptr(rows.col), N.ptr(W), b1 - b0, I, N.ptr(Fb),
-            Fb.stride(0), N.stream_handle(dev)), "lg_spread_resource_f64")
+    for b0, b1, Fb in _f_blocks(rows, W):
         v, i = rows_topk(Fb[:, c64], k, exc.slice_rows(b0, b1) if exc is not None else None,
                          drop, None if eu_r is None else eu_r[b0:b1], eic)
         vals[b0:b1], idxs[b0:b1] = v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
