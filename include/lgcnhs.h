@@ -542,6 +542,58 @@ int lg_hybrid_recip_f64(const double *k_item, int64_t n_items, double lambda, do
 int lg_inv_degree_f64(const int64_t *rowptr, int64_t n_rows, double *inv,
                       lg_stream_t stream);
 
+/* Spreading for item baskets that are not rows of A (csrc/spread_rows.hip K3r): the F row of
+ * getSpreadingGeneralMat / HybridS / getResource (model/SpreadMethod/model.py:14-27, 63-85,
+ * 88-99) for any 0/1 row B over the items -- a new visitor's cart, a session, one item --
+ * regrouped so that no I x I matrix and no tile is built:
+ *     T[v] = inv_ku[v] * sum_{i in items(v), i in B} ra[i]      lg_spread_rows_weight_f64
+ *     F[j] = rb[j]     * sum_{v in users(j)}         T[v]       lg_spread_rows_resource_f64
+ * (ra, rb: lg_hybrid_recip_f64; inv_ku: lg_inv_degree_f64), one sweep of A by user and one of
+ * A by item for a block of at most LG_SPREAD_ROWS_BLOCK baskets. The baskets of the block are a
+ * CSR (basket_rowptr int64 [n_baskets + 1], offsets into basket_items int32; an id outside
+ * [0, n_items) is skipped, an item named twice counts once).
+ *
+ * The order of every sum is a function of the one list it runs over: the terms of a basket are
+ * added one at a time in ascending position of the list, from +0.0; a list longer than
+ * LG_SPREAD_ROWS_SEG positions is cut at multiples of it, each segment summed so, and the
+ * segments' sums added in segment order. It does not depend on the grid, the device, the
+ * block's other baskets, the basket's place in the block or timing; there is no floating-point
+ * atomic. Users whose T row is zero are skipped by test (their mark word is 0), which changes
+ * no bit. The lists longer than LG_SPREAD_ROWS_SEG are named by the caller, once per A:
+ * long_ids (device, int32 [n_long], ascending list ids) and long_ptr (device, int64
+ * [n_long + 1], the exclusive prefix sum of ceil(len / LG_SPREAD_ROWS_SEG)), n_long_units =
+ * long_ptr[n_long]; both NULL with n_long = 0. A long user missing from the table counts as a
+ * zero T row (its mark word is cleared), a long item missing from it gets no F column written;
+ * no table makes a kernel read or write outside the arrays.
+ *
+ * T is [n_users, n_baskets] fp64 (leading dimension n_baskets) and user_marks one 64-bit word
+ * per user, bit b set iff T[v, b] != 0: only those entries of T are written by pass 1 and read
+ * by pass 2 (T needs no clearing), every word of user_marks is written. F is [n_baskets, ldf]:
+ * columns [0, n_items) of every row are written, zeros included. ws: device scratch of
+ * lg_spread_rows_weight_ws_bytes(n_items, n_long_units) / lg_spread_rows_resource_ws_bytes(
+ * n_long_units) bytes (the per-item basket words and the segments' partial sums). LG_ERR_ARG,
+ * before any launch, on a null pointer, n_baskets outside [1, LG_SPREAD_ROWS_BLOCK], negative
+ * or >= 2^31-1 sizes, ldf < n_items, a bad long-list table size, and on a NULL or short
+ * workspace (the message names ws_bytes). */
+#define LG_SPREAD_ROWS_BLOCK 64
+#define LG_SPREAD_ROWS_SEG 4096
+size_t lg_spread_rows_weight_ws_bytes(int64_t n_items, int64_t n_long_units);
+int lg_spread_rows_weight_f64(const int64_t *user_rowptr, const int32_t *user_items,
+                              int64_t n_users, int64_t n_items, const double *ra,
+                              const double *inv_ku, const int64_t *basket_rowptr,
+                              const int32_t *basket_items, int32_t n_baskets,
+                              const int32_t *long_ids, const int64_t *long_ptr, int64_t n_long,
+                              int64_t n_long_units, double *T, uint64_t *user_marks, void *ws,
+                              size_t ws_bytes, lg_stream_t stream);
+size_t lg_spread_rows_resource_ws_bytes(int64_t n_long_units);
+int lg_spread_rows_resource_f64(const int64_t *item_rowptr, const int32_t *item_users,
+                                int64_t n_items, int64_t n_users, const double *T,
+                                const uint64_t *user_marks, const double *rb,
+                                int32_t n_baskets, const int32_t *long_ids,
+                                const int64_t *long_ptr, int64_t n_long, int64_t n_long_units,
+                                double *F, int64_t ldf, void *ws, size_t ws_bytes,
+                                lg_stream_t stream);
+
 /* Line format of a tile (lgcnhs_ref.h lg_spread_tile_rows_f64 builds one tile at a time):
  * row i of general_W restricted to the tile as one 128-byte line at lines + 128 i (32
  * uint32 words) plus, for rows that do not fit, a run of 16-byte units in ovf. Word 0 =

@@ -28,6 +28,8 @@ LG_RANK_ROW_MAX = 4  # include/lgcnhs.h
 LG_ROWS_RANK_ROW_MAX = 1024  # include/lgcnhs.h
 LG_SPREAD_RANK_ROW_MAX = 8  # include/lgcnhs.h
 LG_SPREAD_RANK_VALUES, LG_SPREAD_RANK_COUNTS = 0, 1
+LG_SPREAD_ROWS_BLOCK = 64  # include/lgcnhs.h
+LG_SPREAD_ROWS_SEG = 4096  # include/lgcnhs.h
 ABI_VERSION = 17
 
 _vp = ctypes.c_void_p
@@ -152,6 +154,18 @@ SIGNATURES = {
     ),
     "lg_hybrid_recip_f64": (ctypes.c_int, [_vp, _i64, _f64, _vp, _vp, _vp]),
     "lg_inv_degree_f64": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "lg_spread_rows_weight_ws_bytes": (_sz, [_i64, _i64]),
+    "lg_spread_rows_weight_f64": (
+        ctypes.c_int,
+        [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+         _sz, _vp],
+    ),
+    "lg_spread_rows_resource_ws_bytes": (_sz, [_i64]),
+    "lg_spread_rows_resource_f64": (
+        ctypes.c_int,
+        [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _sz,
+         _vp],
+    ),
     "lg_spread_group_cursor": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
                                               _vp, _vp, _vp, _vp]),
     "lg_spread_group_bound": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp]),

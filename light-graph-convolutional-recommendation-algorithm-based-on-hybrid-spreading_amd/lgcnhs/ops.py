@@ -18,6 +18,9 @@ spread_topk_tiled  the above over item tiles,     (same; for catalogs whose I x 
 spread_recommend   dense or tiled, whichever fits  model/SpreadMethod/recommend.py:59-115
                    (items=: over a candidate item set -- csrc/rows_topk_items.hip on the
                    dense path, a column view of the tiles on the tiled one)
+spread_rows_recommend  the same for item baskets   (no I x I matrix, no tile: two sweeps of
+spread_rows_rank       that are not rows of A        A per 64 baskets, csrc/spread_rows.hip,
+spread_related_items   (a cart, a session, an item)  finished by rows_topk / rows_rank)
 """
 from __future__ import annotations
 
@@ -1200,6 +1203,16 @@ class Interactions:
         self.n_users, self.n_items = by_user.n_rows, by_user.n_cols
         self.k_user = by_user.degrees().to(torch.float64)
         self.k_item = self.by_item.degrees().to(torch.float64)
+        self._rows_long = None
+
+    @property
+    def rows_long(self):
+        """(by user, by item) long-list tables of the basket spreading (_long_lists: the lists
+        longer than SPREAD_ROWS_SEG), built on first use from by_user / by_item as they stand
+        then -- an Interactions is not edited after construction."""
+        if self._rows_long is None:
+            self._rows_long = (_long_lists(self.by_user), _long_lists(self.by_item))
+        return self._rows_long
 
     @classmethod
     def from_pairs(cls, users, items, n_users, n_items, device=None):
@@ -2684,3 +2697,275 @@ def _spread_topk_items(A: Interactions, W: torch.Tensor, ids, cand: torch.Tensor
                          drop, None if eu_r is None else eu_r[b0:b1], eic)
         vals[b0:b1], idxs[b0:b1] = v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
     return vals, idxs
+
+
+# ------------------------------------------- spreading for item baskets outside the graph
+# baskets per call of lg_spread_rows_weight_f64 / lg_spread_rows_resource_f64 (lane b of a wave
+# owns basket b) and the positions per segment of a long list (csrc/spread_rows.hip)
+SPREAD_ROWS_BLOCK = N.LG_SPREAD_ROWS_BLOCK
+SPREAD_ROWS_SEG = N.LG_SPREAD_ROWS_SEG
+
+
+def _basket_rows(rows, n_items: int, device) -> RowSets:
+    """The baskets of a spread_rows_* call as a RowSets over the items, one row per basket:
+    a RowSets (taken as it is), a list of id lists, a dict {row: ids} (rows 0 .. max key) or a
+    (rows, items) pair -- candidate_rows' forms and checks (host ids sorted and de-duplicated:
+    an item named twice counts once, A is 0/1)."""
+    if isinstance(rows, RowSets):
+        if rows.n_cols != n_items:
+            raise ValueError(f"baskets over {rows.n_cols} items, A has {n_items}")
+        if rows.col.device != torch.device(device):
+            raise ValueError(f"rows are on {rows.col.device}, A on {device}")
+        return rows
+    if isinstance(rows, dict):
+        n = max((int(r) for r in rows), default=-1) + 1
+    elif isinstance(rows, tuple) and len(rows) == 2:
+        r = torch.as_tensor(rows[0])
+        n = int(r.max()) + 1 if r.numel() else 0
+    else:
+        rows = list(rows)
+        n = len(rows)
+    return candidate_rows(rows, n, n_items, device)
+
+
+def _long_lists(rs: RowSets):
+    """(long_ids int32, long_ptr int64, n_long, n_units): the lists of ``rs`` longer than
+    SPREAD_ROWS_SEG and the exclusive prefix sum of their segment counts, as the
+    lg_spread_rows_* entries take them (both None when no list is long). One host read."""
+    deg = rs.degrees()
+    ids = torch.nonzero(deg > SPREAD_ROWS_SEG).reshape(-1)
+    n_long = int(ids.numel())
+    if n_long == 0:
+        return None, None, 0, 0
+    ptr = torch.zeros(n_long + 1, dtype=torch.int64, device=deg.device)
+    torch.cumsum((deg[ids] + SPREAD_ROWS_SEG - 1) // SPREAD_ROWS_SEG, 0, out=ptr[1:])
+    return ids.to(torch.int32), ptr, n_long, int(ptr[-1])
+
+
+class _RowsPlan:
+    """What the two passes read besides the baskets: ra / rb / inv_ku of (A, lam), computed
+    once per call, the long-list tables (they depend on A alone: kept on it), the workspaces,
+    T and the users' mark words for blocks of at most ``nb_max`` baskets."""
+
+    def __init__(self, A: "Interactions", lam: float, nb_max: int):
+        N.require_gpu(A.k_item, "A")
+        dev = A.k_item.device
+        self.A, self.dev = A, dev
+        self.ra, self.rb = hybrid_recip(A.k_item, lam)
+        self.inv_ku = torch.empty(max(1, A.n_users), dtype=torch.float64, device=dev)
+        N.check(N.lib().lg_inv_degree_f64(N.ptr(A.by_user.rowptr), A.n_users,
+                                          N.ptr(self.inv_ku), N.stream_handle(dev)),
+                "lg_inv_degree_f64")
+        self.long_u, self.long_i = A.rows_long
+        self._one = None
+        self.u_col = A.by_user.col if A.by_user.col.numel() else self._stand_in()
+        self.i_col = A.by_item.col if A.by_item.col.numel() else self._stand_in()
+        nb_max = max(1, min(int(nb_max), SPREAD_ROWS_BLOCK))
+        self.T = torch.empty(max(1, A.n_users * nb_max), dtype=torch.float64, device=dev)
+        self.marks = torch.empty(max(1, A.n_users), dtype=torch.int64, device=dev)
+        self.ws1 = torch.empty(
+            max(1, N.lib().lg_spread_rows_weight_ws_bytes(A.n_items, self.long_u[3])),
+            dtype=torch.uint8, device=dev)
+        self.ws2 = torch.empty(max(1, N.lib().lg_spread_rows_resource_ws_bytes(self.long_i[3])),
+                               dtype=torch.uint8, device=dev)
+
+    def _stand_in(self) -> torch.Tensor:
+        """A one-element int32 array for an empty one (an empty tensor has no pointer to pass and
+        the entries refuse NULL; never read: no row points into it), made on first need."""
+        if self._one is None:
+            self._one = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        return self._one
+
+    def run(self, B: RowSets, b0: int, b1: int, F: torch.Tensor, evs=None) -> None:
+        """F[:b1 - b0, :I] = the F rows of baskets [b0, b1) of B (at most SPREAD_ROWS_BLOCK)."""
+        A, s = self.A, N.stream_handle(self.dev)
+        nb = b1 - b0
+        lu, li = self.long_u, self.long_i
+        b_col = B.col if B.col.numel() else self._stand_in()
+        _mark(evs, "pass1")
+        N.check(N.lib().lg_spread_rows_weight_f64(
+            N.ptr(A.by_user.rowptr), N.ptr(self.u_col), A.n_users, A.n_items,
+            N.ptr(self.ra), N.ptr(self.inv_ku), N.ptr(B.rowptr[b0:]), N.ptr(b_col), nb,
+            N.ptr(lu[0]), N.ptr(lu[1]), lu[2], lu[3], N.ptr(self.T), N.ptr(self.marks),
+            N.ptr(self.ws1), self.ws1.numel(), s), "lg_spread_rows_weight_f64")
+        _mark(evs, "pass2")
+        N.check(N.lib().lg_spread_rows_resource_f64(
+            N.ptr(A.by_item.rowptr), N.ptr(self.i_col), A.n_items, A.n_users,
+            N.ptr(self.T), N.ptr(self.marks), N.ptr(self.rb), nb, N.ptr(li[0]), N.ptr(li[1]),
+            li[2], li[3], N.ptr(F), F.stride(0), N.ptr(self.ws2), self.ws2.numel(), s),
+            "lg_spread_rows_resource_f64")
+        _mark(evs, None)
+
+
+def _rows_fill(plan: _RowsPlan, B: RowSets, b0: int, b1: int, F: torch.Tensor, evs=None):
+    """F[:b1 - b0] = the F rows of baskets [b0, b1), SPREAD_ROWS_BLOCK of them per call."""
+    for c0 in range(b0, b1, SPREAD_ROWS_BLOCK):
+        c1 = min(b1, c0 + SPREAD_ROWS_BLOCK)
+        plan.run(B, c0, c1, F[c0 - b0:c1 - b0], evs)
+
+
+def spread_rows_resource(A: Interactions, rows, lam: float,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """F [n, I] fp64 for n item baskets that need not be rows of A -- a new visitor's cart, a
+    session, one item: F[b] = B_b @ HybridS(A, general_W, lam), the row spread_resource gives a
+    user with exactly those items, computed as
+        T[v] = fl(1/k_v) * sum_{i in items(v), i in B_b} ra_i,   F[b, j] = rb_j * sum_{v in users(j)} T[v]
+    by two sweeps of A per block of SPREAD_ROWS_BLOCK baskets (lg_spread_rows_weight_f64,
+    lg_spread_rows_resource_f64), with no I x I matrix and no tile. Within 1e-12 relative of the
+    dense rows @ spread_hybrid(A, lam), exact zeros where that has them. Every sum runs in the
+    order of its own list (csrc/spread_rows.hip): row b is bitwise the one-basket call's row,
+    whatever the other baskets, their number and order.
+
+    rows: a RowSets over the items, a list of id lists, a dict {row: ids} or a (rows, items)
+    pair (candidate_rows' forms; items named twice count once). out: as in spread_resource."""
+    I = A.n_items
+    dev = A.k_item.device
+    B = _basket_rows(rows, I, dev)
+    n = B.n_rows
+    if out is not None:
+        _typed(out, "out", torch.float64)
+        if out.shape[0] < n or out.shape[1] < I or (out.numel() and out.stride(1) != 1):
+            raise ValueError(f"out has shape {tuple(out.shape)} strides {out.stride()}, "
+                             f"expected at least ({n}, {I}) with unit column stride")
+        _same_device(out, "out", A.k_item, "A")
+    N.require_gpu(A.k_item, "A")
+    F = out if out is not None else torch.empty((n, I), dtype=torch.float64, device=dev)
+    if n and I:
+        _rows_fill(_RowsPlan(A, lam, n), B, 0, n, F)
+    return F
+
+
+def _rows_f_blocks(A: Interactions, B: RowSets, lam: float, W, evs=None):
+    """Yield (b0, b1, Fb) over blocks of the baskets' F rows in one reused buffer, F_BLOCK_BYTES
+    of F per block: the two passes, or with W (checked by the caller) _f_blocks' dense rows."""
+    if W is not None:
+        yield from _f_blocks(B, W)
+        return
+    n, I = B.n_rows, B.n_cols
+    block = max(1, min(n, F_BLOCK_BYTES // max(1, I * 8)))
+    plan = _RowsPlan(A, lam, block)
+    buf = torch.empty((block, I), dtype=torch.float64, device=plan.dev)
+    for b0 in range(0, n, block):
+        b1 = min(n, b0 + block)
+        _rows_fill(plan, B, b0, b1, buf, evs)
+        yield b0, b1, buf[: b1 - b0]
+
+
+def _rows_guard(A, rows, excl, drop, eu, ei, W):
+    """(B, ex) of a spread_rows_* call, every argument checked before the library is reached."""
+    I = A.n_items
+    dev = A.k_item.device
+    B = _basket_rows(rows, I, dev)
+    n = B.n_rows
+    if eu is not None or ei is not None:
+        _g_guard(eu, ei, n, I, f"{n} baskets over {I} items: ")
+    if excl is not None and not isinstance(excl, RowSets):
+        raise TypeError(f"excl must be a RowSets or None, got {type(excl).__name__}")
+    # None: the reference drops what the user already has (drop=False: nothing to keep out)
+    ex = (B if drop else None) if excl is None else excl
+    _excl_guard(ex, n, "baskets", eu is not None and not drop)
+    if ex is not None and ex.col.device != B.col.device:
+        raise ValueError(f"excl is on {ex.col.device}, A on {B.col.device}")
+    if W is not None:
+        _check_W(W, I, f"the fp64 ({I}, {I}) matrix of spread_hybrid")
+        _same_device(W, "W", A.k_item, "A")
+    return B, ex
+
+
+def spread_rows_recommend(A: Interactions, rows, lam: float, k: int,
+                          excl: RowSets | None = None, drop: bool = True,
+                          eu: torch.Tensor | None = None, ei: torch.Tensor | None = None,
+                          items=None, W: torch.Tensor | None = None, stats: dict | None = None):
+    """Top-k of (G *) spread_rows_resource(A, rows, lam) per basket: (values fp64 [n, k], item
+    ids int64 [n, k], {-inf, -1} padding), rows_topk's order and modes, k <= 1024. F is computed
+    F_BLOCK_BYTES at a time and never all held.
+
+    excl: None drops each basket's own items (drop=False keeps them), else a RowSets with one
+    row per basket. eu: [n, d] float32, one row per basket, supplied by the caller (an unseen
+    user has no learned embedding); ei: the item table. items: a candidate item set in
+    item_candidates' forms -- F[:, C] is gathered and ranked with the exclusions renumbered and
+    ei[C], real item ids in the lists. W: a prebuilt spread_hybrid(A, lam) sends the baskets
+    through the dense path (_blocks_topk; lam is then not read). stats: a dict that receives
+    t_setup_ms / t_pass1_ms / t_pass2_ms / t_topk_ms (HIP events; one synchronize)."""
+    k = int(k)
+    if k < 1 or k > 1024:
+        raise ValueError(f"k={k} not in [1, 1024]")
+    if isinstance(items, slice):
+        raise ValueError("spread_rows_recommend: items= is a candidate set (ids or a mask)")
+    B, ex = _rows_guard(A, rows, excl, drop, eu, ei, W)
+    dev = A.k_item.device
+    n, I = B.n_rows, A.n_items
+    cand = None if items is None else item_candidates(items, I, dev)
+    N.require_gpu(A.k_item, "A")
+    if W is not None and cand is None:
+        return _blocks_topk(B, W, k, _nonempty(ex), drop, eu, ei)
+    vals = torch.full((n, k), float("-inf"), dtype=torch.float64, device=dev)
+    idxs = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    if n == 0 or I == 0 or (cand is not None and cand.numel() == 0):
+        return vals, idxs
+    evs = [] if stats is not None else None
+    _mark(evs, "setup")
+    if cand is not None:
+        c64 = cand.to(torch.int64)
+        ex = ex.restrict_cols(cand) if ex is not None else None
+        eic = None if ei is None else ei[c64]
+    ex = _nonempty(ex)
+    for b0, b1, Fb in _rows_f_blocks(A, B, lam, W, evs):
+        _mark(evs, "topk")
+        exb = ex.slice_rows(b0, b1) if ex is not None else None
+        eub = None if eu is None else eu[b0:b1]
+        if cand is None:
+            vals[b0:b1], idxs[b0:b1] = rows_topk(Fb, k, exb, drop, eub, ei)
+        else:
+            v, i = rows_topk(Fb[:, c64], k, exb, drop, eub, eic)
+            vals[b0:b1], idxs[b0:b1] = v, torch.where(i >= 0, c64[i.clamp(min=0)], i)
+        _mark(evs, "setup")
+    if evs is not None:
+        _mark(evs, None)
+        _stage_ms(stats, evs, dev, "setup", "pass1", "pass2", "topk")
+    return vals, idxs
+
+
+def spread_rows_rank(A: Interactions, rows, lam: float, targets, excl: RowSets | None = None,
+                     drop: bool = True, eu: torch.Tensor | None = None,
+                     ei: torch.Tensor | None = None):
+    """Where given items stand among ALL items under spread_rows_recommend's scores -- given
+    half a basket, where does the other half rank: (rank int64 [nnz], value fp64 [nnz]) aligned
+    with the target CSR's col, rows_rank's definitions. For any k <= 1024, rank < k iff
+    spread_rows_recommend(A, rows, lam, k, excl, drop, eu, ei) holds the item at [row, rank],
+    with a bit-equal value; a dropped target gets -1. targets: anything candidate_rows takes,
+    one row per basket."""
+    B, ex = _rows_guard(A, rows, excl, drop, eu, ei, None)
+    dev = A.k_item.device
+    n, I = B.n_rows, A.n_items
+    if isinstance(targets, RowSets) and targets.n_rows != n:
+        raise ValueError(f"target rows {targets.n_rows} != {n} baskets")
+    targets = candidate_rows(targets, n, I, dev)
+    N.require_gpu(A.k_item, "A")
+    nnz = int(targets.col.numel())
+    rank = torch.full((nnz,), -1, dtype=torch.int64, device=dev)
+    val = torch.full((nnz,), float("-inf"), dtype=torch.float64, device=dev)
+    if n == 0 or nnz == 0 or I == 0:
+        return rank, val
+    ex = _nonempty(ex)
+    for b0, b1, Fb in _rows_f_blocks(A, B, lam, None):
+        rows_rank(Fb, targets.slice_rows(b0, b1),
+                  ex.slice_rows(b0, b1) if ex is not None else None, drop,
+                  None if eu is None else eu[b0:b1], ei, out=(rank, val))
+    return rank, val
+
+
+def spread_related_items(A: Interactions, item_ids, lam: float, k: int, items=None):
+    """"Related to this item": spread_rows_recommend for one single-item basket per entry of
+    item_ids (any order, duplicates allowed), the item itself dropped."""
+    t = torch.as_tensor(item_ids)
+    if t.numel() and (t.dtype == torch.bool or t.is_floating_point() or t.is_complex()):
+        raise ValueError("item ids must be integers")
+    t = t.reshape(-1).to(torch.int64)
+    if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= A.n_items):
+        raise ValueError(f"item id outside [0, {A.n_items})")
+    dev = A.k_item.device
+    n = int(t.numel())
+    B = RowSets(torch.arange(n + 1, dtype=torch.int64, device=dev), t.to(dev, torch.int32), n,
+                A.n_items)
+    return spread_rows_recommend(A, B, lam, k, items=items)

@@ -60,6 +60,29 @@ def spread_lightgcn_topk(model, user_num: int, item_num: int, train_data_df: pd.
                                 tiled=tiled, users=users, items=items)
 
 
+def spread_lightgcn_baskets(model, baskets: dict, basket_emb, user_num: int, item_num: int,
+                            train_data_df: pd.DataFrame, val_data_df: pd.DataFrame,
+                            lambda_val: float, k: int, device=None, items=None) -> dict:
+    """{key: [items]} of the LGCNHS scores G * F for item baskets {key: item ids} outside the
+    graph: F by ops.spread_rows_recommend (two sweeps of the interactions), G from the
+    caller's ``basket_emb`` -- one float32 row per basket, in the dict's order: an unseen user
+    has no learned e0, the caller decides what stands for it -- and model.items_emb.weight.
+    The basket's own items are dropped; lists hold real item ids and come out shorter when
+    fewer than k items rank. ``items``: rank only those items. Nothing is written."""
+    dev = device or gpu_device(model.items_emb.weight)
+    both = pd.concat([train_data_df, val_data_df])
+    inter = ops.Interactions.from_pairs(
+        torch.from_numpy(both["user_id"].to_numpy(np.int64)),
+        torch.from_numpy(both["item_id"].to_numpy(np.int64)), user_num, item_num, dev)
+    eu = torch.as_tensor(basket_emb).detach().to(dev, torch.float32).contiguous()
+    ei = model.items_emb.weight.detach().to(dev, torch.float32).contiguous()
+    keys = list(baskets)
+    _, idx = ops.spread_rows_recommend(inter, [baskets[key] for key in keys], lambda_val, k,
+                                       eu=eu, ei=ei, items=items)
+    lists = topk_to_dict(idx)
+    return {key: lists[r] for r, key in enumerate(keys)}
+
+
 def spread_lightgcn_ranks(model, user_num: int, item_num: int, train_data_df: pd.DataFrame,
                           val_data_df: pd.DataFrame, held_df: pd.DataFrame, lambda_val: float,
                           device=None, users=None, tiled: bool | None = None,

@@ -73,6 +73,34 @@ def spread_method_topk(user_num: int, item_num: int, train_data_df: pd.DataFrame
                                 items=items)
 
 
+def recommendForBaskets(baskets: dict, user_num: int, item_num: int,
+                        train_data_df: pd.DataFrame, val_data_df: pd.DataFrame, method: str,
+                        lambda_val: float, dataset: str, k: int, items=None,
+                        device=None) -> dict:
+    """{key: [items]} for item baskets {key: item ids} that need not belong to any user of the
+    DataFrames -- a new visitor's cart, a session, one item: per basket the k best items of
+    B @ HybridS(A, general_W, lambda) not in the basket (the reference's scores and filter,
+    :31-50, for the user such a basket would be), by ops.spread_rows_recommend: two sweeps of
+    the interactions, no I x I matrix at any catalog size. ``method`` / ``dataset`` resolve as
+    in spread_method_topk (general_W is exactly symmetric: the transposes change nothing).
+    ``items``: rank only those items (ops.item_candidates' forms). Lists hold real item ids;
+    a basket with fewer than k rankable items gets a shorter list. Nothing is written."""
+    dev = device or gpu_device()
+    both = pd.concat([train_data_df, val_data_df])
+    inter = ops.Interactions.from_pairs(
+        torch.from_numpy(both["user_id"].to_numpy(np.int64)),
+        torch.from_numpy(both["item_id"].to_numpy(np.int64)), user_num, item_num, dev)
+    if method == "ProbS" and dataset == "movielens":  # reference :87-91
+        lambda_val = 0.01
+    elif method == "HeatS" and dataset == "douban":  # reference :97-101
+        lambda_val = 0.99
+    keys = list(baskets)
+    _, idx = ops.spread_rows_recommend(inter, [baskets[key] for key in keys], lambda_val, k,
+                                       items=items)
+    lists = topk_to_dict(idx)
+    return {key: lists[r] for r, key in enumerate(keys)}
+
+
 def held_out_rows(held_df: pd.DataFrame, user_num: int, item_num: int, dev, users=None):
     """The held-out positives of a DataFrame (user_id, item_id) as target rows: one sorted
     row per user, or per entry of ``users`` in that order."""
